@@ -7,7 +7,12 @@ forward (3 student blocks + teacher, 4 warp-pair launches) + L1/distillation los
 AdamW.  Warps, loss / merge epilogues, resizes and the 3-D convolutions (implicit GEMM on the fp32 matrix
 cores) are this repo's HIP kernels behind the C-ABI; what is left to ATen is listed in DESIGN.md §5.
 
-In the K timed steps only the launches of the dominant entry point (found in the warm-up steps: ~90 of ~540
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`,
+...).  `--dump-outputs DIR` writes what the last timed step returned (DIR/<name>.npy, see dump_outputs()).  Everything
+below -- per-launch records, roofline, eager figure, parity witnesses, C2 / C3 legs, CPU baseline -- runs only with
+`--full`.
+
+With --full: in the K timed steps only the launches of the dominant entry point (found in the warm-up steps: ~90 of ~540
 launches per step) carry HIP events on the launch stream, so `roofline` is measured inside the timed region at no
 visible cost; a short separate pass afterwards (same model, same batch) records every C-ABI launch for the
 `kernels` table.  After
@@ -16,7 +21,8 @@ model on the same batches from the same seed: `parity_at_cpu_size` is the bench 
 (the run exits non-zero when the losses disagree by more than 5e-4 relative).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
-    python bench.py --gpus 8 --steps 5 --warmup 2          # starts its own 8 rank processes (see launch())
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full  # + everything the headline does not need
+    python bench.py --gpus 8 --steps 5 --warmup 2         # starts its own 8 rank processes (see launch())
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -215,6 +221,28 @@ def parity_at_bench_size(dev):
     return rec
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept of a larger output (4 MB in float32; six such outputs at 2 x 256^3)
+
+
+def dump_outputs(out_dir, pred, info):
+    """What the timed step returned in its last step -- `pred` (the merged frame) and every entry of `info` (flows,
+    teacher frame, masks, losses) -- as out_dir/<name>.npy in float32.  An output of more than DUMP_SAMPLE elements is
+    written as DUMP_SAMPLE of its elements (flattened, ascending positions) drawn from a generator seeded the same for
+    every output and every run, so that two builds given the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in sorted(dict(info, pred=pred).items()):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(1234)).sort().values
+            t = t[idx.to(t.device)]
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64e6, "dump of %d bytes exceeds 64 MB" % total
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -241,7 +269,16 @@ def parse():
     ap.add_argument("--config-steps", type=int, default=20, help="timed steps of the C2 / C3 legs")
     ap.add_argument("--record-steps", type=int, default=2,
                     help="steps of the separate per-launch recording pass (roofline / kernels entries)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-launch kernel records and rooflines, the eager "
+                         "step time, parity_at_bench_size, the C2 / C3 legs and the CPU baseline (the --no-* options, "
+                         "--cpu-size, --config-steps and --record-steps act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, <= 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def usable_cores():
@@ -703,18 +740,16 @@ def main():
         do_step = lambda: graph_step(imgs, gt, lr)
     else:
         do_step = eager_step
-    # warm-up: every C-ABI launch is recorded (HIP events on the launch stream) -- this warms the event pool
-    # and tells which entry point dominates the step
-    ops.enable_kernel_timing(True)
+    # warm-up (--full): every C-ABI launch is recorded (HIP events on the launch stream) -- this warms the event pool
+    # and tells which entry point dominates the step.  The first warm-up step is eager in a plain run too, so that the
+    # model takes the same steps with and without --full.
+    ops.enable_kernel_timing(args.full)
     for i in range(args.warmup):
         eager_step() if (use_graph and i == 0) else do_step()  # (one eager step: the warm-up's per-launch records)
         torch.cuda.synchronize()
         if rank == 0:
             log("warm-up step %d done" % i)
     wt = ops.kernel_timings()
-    # the dominant KERNEL of the warm-up steps: the symbol with the largest total time among the launches ops.py can
-    # name (the Winograd trunk kernels; `rocprofv3 --kernel-trace --stats` of this command, profiles/, names the same
-    # one); its entry point is the one followed with events inside the timed region
     # the dominant KERNEL of the warm-up steps: kernel symbols ops.py can name and, per entry point, the launches it
     # cannot (the same candidates the final `roofline` record is chosen from); its entry point is the one followed with
     # events inside the timed region
@@ -722,9 +757,9 @@ def main():
     dom_sym = max(wsym, key=lambda k: sum(r[0] for r in wsym[k][1])) if wsym else None
     dom_guess = wsym[dom_sym][0] if dom_sym else (max(wt, key=lambda k: sum(r[0] for r in wt[k])) if wt else None)
     barrier()
-    # timed region: only that entry point's launches carry events (~90 of ~430 launches per step), so the headline
-    # time is free of profiling overhead while `roofline` is still measured inside the region
-    ops.enable_kernel_timing(True, only=[dom_guess] if dom_guess else None)
+    # timed region (--full): only that entry point's launches carry events (~90 of ~430 launches per step), so the
+    # headline time is free of profiling overhead while `roofline` is still measured inside the region
+    ops.enable_kernel_timing(args.full, only=[dom_guess] if dom_guess else None)
     t0 = time.perf_counter()
     step_marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     step_marks[0].record()
@@ -733,9 +768,11 @@ def main():
         step_marks[i + 1].record()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pred, info)
     timed = ops.kernel_timings()
     eager_dt = None
-    if use_graph:
+    if args.full and use_graph:
         # a replayed graph carries no per-launch events: the same K steps once more as eager launches, right behind the
         # timed region, give the eager step time (`step_drivers`) and the dominant kernel's launch durations (`roofline`)
         ops.enable_kernel_timing(True, only=[dom_guess] if dom_guess else None)
@@ -748,9 +785,10 @@ def main():
         timed = ops.kernel_timings()
     # separate recording pass (outside the timed region) for the per-entry-point `kernels` table
     ksteps = max(1, args.record_steps)
-    ops.enable_kernel_timing(True)
-    for _ in range(ksteps):
-        model.update(imgs, gt, learning_rate=lr, training=True)
+    if args.full:
+        ops.enable_kernel_timing(True)
+        for _ in range(ksteps):
+            model.update(imgs, gt, learning_rate=lr, training=True)
     ktimes = ops.kernel_timings()
     ops.enable_kernel_timing(False)
     loss = float(info["loss_G"].detach())
@@ -787,36 +825,6 @@ def main():
     dt = float(t.item())
 
     if rank == 0:
-        kern = {name: _aggregate(recs, ksteps) for name, recs in ktimes.items()}
-        ksym = {sym: dict(_aggregate(recs, ksteps), entry_point=ep) for sym, (ep, recs) in by_symbol(ktimes).items()}
-        # `roofline` = the dominant hand-written KERNEL (by symbol, as rocprofv3's kernel stats name it); its record
-        # comes from the events recorded inside the timed region when its entry point was the one followed there
-        # `roofline` is the dominant hand-written KERNEL among the symbols ops.py can name (what `rocprofv3 --kernel-trace
-        # --stats` of this command lists first).  Launches it cannot name are filed under their entry point, which may
-        # stand for several kernels: the largest such group and the named kernel's share of the step are reported beside
-        # the record (`named_kernel_share_of_step`, `largest_unnamed_entry_point`), so that a reader sees when the named
-        # kernel is not what dominates
-        unnamed = {}
-        for ep, recs in ktimes.items():
-            rest = [r for r in recs if not (len(r) > 4 and r[4])]
-            if rest:
-                unnamed[ep] = _aggregate(rest, ksteps)
-        dom = max(ksym, key=lambda k: ksym[k]["ms_per_step"]) if ksym else max(kern, key=lambda k: kern[k]["ms_per_step"])
-        dom_rec = (ksym if ksym else kern)[dom]
-        big_unnamed = max(unnamed, key=lambda k: unnamed[k]["ms_per_step"]) if unnamed else None
-        dom_src = "HIP events, separate pass of %d steps after the timed region" % ksteps
-        tsym = by_symbol(timed)
-        if dom in tsym:
-            dom_rec = dict(_aggregate(tsym[dom][1], args.steps), entry_point=tsym[dom][0])
-            dom_src = "HIP events on the launch stream inside the timed region (%d launches)" % dom_rec["launches"]
-        elif dom in timed and timed[dom]:
-            dom_rec = _aggregate(timed[dom], args.steps)
-            dom_src = "HIP events on the launch stream inside the timed region (%d launches)" % dom_rec["launches"]
-        if use_graph and "inside the timed region" in dom_src:
-            dom_src = ("HIP events on the launch stream inside the eager pass of %d steps run right behind the graph-replayed "
-                       "timed region (a replayed graph carries no per-launch events; %d launches)" % (args.steps, dom_rec["launches"]))
-        # the entry point with the largest total time, for continuity with rounds 1-3 (same definition of `frac` now)
-        dom_ep = max(kern, key=lambda k: kern[k]["ms_per_step"])
         out = {
             "metric": "volume-pairs/sec, Flow-3D unsupervised train step (fwd+loss+bwd+AdamW)",
             "value": world * B * args.steps / dt,
@@ -833,36 +841,68 @@ def main():
                                    "3D trilinear warp HIP kernels" % (args.dataset, S, B),
                        "global_batch": world * B, "volume": [S, S, S],
                        "parallelism": "dp%d" % world},
-            "roofline": dict(roofline(dom, dom_rec, S, B), launches=dom_rec["launches"], avg_ms=dom_rec["avg_ms"],
-                             ms_per_step=dom_rec["ms_per_step"], entry_point=dom_rec.get("entry_point", dom),
-                             measured=dom_src,
-                             named_kernel_share_of_step=round(dom_rec["ms_per_step"] / (dt / args.steps * 1e3), 4),
-                             largest_unnamed_entry_point=(None if big_unnamed is None else
-                                                          {"entry_point": big_unnamed, "ms_per_step": unnamed[big_unnamed]["ms_per_step"],
-                                                           "launches_per_step": unnamed[big_unnamed]["launches"] / ksteps,
-                                                           "note": "several kernels behind one entry point, not one kernel"})),
-            "roofline_entry_point": dict(roofline(dom_ep, kern[dom_ep], S, B), ms_per_step=kern[dom_ep]["ms_per_step"]),
-            # the hot-path row the metric is named after (the trilinear backward warp pair)
-            # against the HBM roofline, with its measured HBM traffic per launch; `roofline` above is the
-            # kernel that dominates the step's time
-            "roofline_hbm": roofline_hbm(kern, ktimes, S, B),
-            "kernels": kern,
-            "kernel_symbols": ksym,
             "loss_G": loss,
             # what in the environment could have changed dispatch or numerics (INTEGRATION.md "Switches")
             "switches": _lib_switches(),
             "deterministic": bool(torch.are_deterministic_algorithms_enabled()),
             "step_driver": "hip-graph replay (Model.graphed_update)" if use_graph else
                            "eager launches (Model.update%s)" % (" under DistributedDataParallel" if ddp else ""),
-            # both drivers on this run's N (N > 1: eager only -- graph capture through DDP's reducer is refused)
-            "step_drivers": {"hip_graph_replay_ms_per_step": (dt / args.steps * 1e3) if use_graph else None,
-                             "eager_ms_per_step": (eager_dt / args.steps * 1e3) if use_graph else dt / args.steps * 1e3,
-                             "default": "hip-graph replay at N = 1 (--eager opts out); eager under DDP"},
         }
         if ranks is not None:
             out["ranks"] = ranks
         rc = 0
-        if world == 1 and S == 256 and not args.no_bench_parity:
+        if args.full:
+            kern = {name: _aggregate(recs, ksteps) for name, recs in ktimes.items()}
+            ksym = {sym: dict(_aggregate(recs, ksteps), entry_point=ep) for sym, (ep, recs) in by_symbol(ktimes).items()}
+            # `roofline` is the dominant hand-written KERNEL among the symbols ops.py can name (what `rocprofv3 --kernel-trace
+            # --stats` of this command lists first); its record comes from the events recorded inside the timed region when
+            # its entry point was the one followed there.  Launches ops.py cannot name are filed under their entry point, which
+            # may stand for several kernels: the largest such group and the named kernel's share of the step are reported
+            # beside the record (`named_kernel_share_of_step`, `largest_unnamed_entry_point`), so that a reader sees when the
+            # named kernel is not what dominates
+            unnamed = {}
+            for ep, recs in ktimes.items():
+                rest = [r for r in recs if not (len(r) > 4 and r[4])]
+                if rest:
+                    unnamed[ep] = _aggregate(rest, ksteps)
+            dom = max(ksym, key=lambda k: ksym[k]["ms_per_step"]) if ksym else max(kern, key=lambda k: kern[k]["ms_per_step"])
+            dom_rec = (ksym if ksym else kern)[dom]
+            big_unnamed = max(unnamed, key=lambda k: unnamed[k]["ms_per_step"]) if unnamed else None
+            dom_src = "HIP events, separate pass of %d steps after the timed region" % ksteps
+            tsym = by_symbol(timed)
+            if dom in tsym:
+                dom_rec = dict(_aggregate(tsym[dom][1], args.steps), entry_point=tsym[dom][0])
+                dom_src = "HIP events on the launch stream inside the timed region (%d launches)" % dom_rec["launches"]
+            elif dom in timed and timed[dom]:
+                dom_rec = _aggregate(timed[dom], args.steps)
+                dom_src = "HIP events on the launch stream inside the timed region (%d launches)" % dom_rec["launches"]
+            if use_graph and "inside the timed region" in dom_src:
+                dom_src = ("HIP events on the launch stream inside the eager pass of %d steps run right behind the graph-replayed "
+                           "timed region (a replayed graph carries no per-launch events; %d launches)" % (args.steps, dom_rec["launches"]))
+            # the entry point with the largest total time, for continuity with rounds 1-3 (same definition of `frac` now)
+            dom_ep = max(kern, key=lambda k: kern[k]["ms_per_step"])
+            out.update({
+                "roofline": dict(roofline(dom, dom_rec, S, B), launches=dom_rec["launches"], avg_ms=dom_rec["avg_ms"],
+                                 ms_per_step=dom_rec["ms_per_step"], entry_point=dom_rec.get("entry_point", dom),
+                                 measured=dom_src,
+                                 named_kernel_share_of_step=round(dom_rec["ms_per_step"] / (dt / args.steps * 1e3), 4),
+                                 largest_unnamed_entry_point=(None if big_unnamed is None else
+                                                              {"entry_point": big_unnamed, "ms_per_step": unnamed[big_unnamed]["ms_per_step"],
+                                                               "launches_per_step": unnamed[big_unnamed]["launches"] / ksteps,
+                                                               "note": "several kernels behind one entry point, not one kernel"})),
+                "roofline_entry_point": dict(roofline(dom_ep, kern[dom_ep], S, B), ms_per_step=kern[dom_ep]["ms_per_step"]),
+                # the hot-path row the metric is named after (the trilinear backward warp pair)
+                # against the HBM roofline, with its measured HBM traffic per launch; `roofline` above is the
+                # kernel that dominates the step's time
+                "roofline_hbm": roofline_hbm(kern, ktimes, S, B),
+                "kernels": kern,
+                "kernel_symbols": ksym,
+                # both drivers on this run's N (N > 1: eager only -- graph capture through DDP's reducer is refused)
+                "step_drivers": {"hip_graph_replay_ms_per_step": (dt / args.steps * 1e3) if use_graph else None,
+                                 "eager_ms_per_step": (eager_dt / args.steps * 1e3) if use_graph else dt / args.steps * 1e3,
+                                 "default": "hip-graph replay at N = 1 (--eager opts out); eager under DDP"},
+            })
+        if args.full and world == 1 and S == 256 and not args.no_bench_parity:
             del pred, info
             pred = info = None
             model = imgs = gt = data = None
@@ -872,7 +912,7 @@ def main():
             if not w["ok"]:
                 log("PARITY FAILURE at the bench size: %s" % json.dumps(w))
                 rc = 4
-        if world == 1 and not args.no_configs and not ddp:
+        if args.full and world == 1 and not args.no_configs and not ddp:
             # the other single-GPU BASELINE configurations, driver-timed in the same run (extra keys; the top-level
             # metric stays config 4's): C2 Flow-2D 160x224 B=16, C3 UPFlow 150x450 B=32 with census.  Their GPU legs
             # run BEFORE any CPU baseline: the oracle's OpenMP team keeps spinning on every host core after its
@@ -886,7 +926,7 @@ def main():
                 log("config %s" % name)
                 out["configs"][name] = fn(dev, args.config_steps, 5)
                 torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], out["parity_at_cpu_size"] = cpu_baseline(args.cpu_size, args.dataset, dev)
             w = out["parity_at_cpu_size"]
             if not (w["rel"] <= w["tolerance_rel"] and w["loss_G_step2_rel"] <= w["tolerance_rel"]

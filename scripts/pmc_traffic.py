@@ -1,7 +1,7 @@
 """HBM bytes per launch of every C-ABI entry point of the bench step, from two rocprofv3 --pmc passes.
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out/f -- python bench.py --steps 2 --warmup 2 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d out/w -- python bench.py --steps 2 --warmup 2 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out/f -- python bench.py --full --steps 2 --warmup 2 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d out/w -- python bench.py --full --steps 2 --warmup 2 --no-cpu-baseline
     python scripts/pmc_traffic.py <f/..counter_collection.csv> <w/..counter_collection.csv> <bench.json> > profiles/rNN_pmc_traffic.json
 
 Counters are collected in their own passes (MI355X_MICROARCH.md: FETCH_SIZE and WRITE_SIZE do not fit one pass);

@@ -1,9 +1,11 @@
 """-m gpu: the bench.py contract on a tiny workload -- ONE JSON line on stdout with the required keys."""
 import json
 import os
+import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +17,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 def test_bench_json_contract():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "32", "--batch", "1", "--steps", "2",
-           "--warmup", "1", "--cpu-size", "32", "48", "--no-configs"]
+           "--warmup", "1", "--cpu-size", "32", "48", "--no-configs", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600,
                        env=dict(os.environ, FLOWSCI_BENCH_NO_CPU_256="1"))
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -65,7 +67,7 @@ def test_bench_line_carries_the_other_single_gpu_configs():
     """C2 (Flow-2D 160x224 B=16) and C3 (UPFlow 150x450 B=32, census on) are timed in the same
     run, as extra keys; the top-level metric stays config 4's."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "32", "--batch", "1", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--config-steps", "3"]
+           "--warmup", "1", "--no-cpu-baseline", "--config-steps", "3", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -85,3 +87,42 @@ def test_bench_line_carries_the_other_single_gpu_configs():
     # the launch-bound C2 step replayed from one HIP graph is not slower than eager
     assert c2["graph_replay"]["ms_per_step"] < c2["eager"]["ms_per_step"] * 1.05
     assert c2["ms_per_step"] == c2["graph_replay"]["ms_per_step"] and c2["step_driver"].startswith("hip-graph replay")
+
+
+PLAIN = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+         "dtype", "data", "config", "loss_G", "step_driver"}
+FULL_ONLY = {"roofline", "roofline_entry_point", "roofline_hbm", "kernels", "kernel_symbols", "step_drivers", "cpu_baseline",
+             "parity_at_cpu_size", "parity_at_bench_size", "configs"}
+OUTPUTS = {"pred", "merged_tea", "mask", "mask_tea", "flow", "flow_tea", "loss_l1", "loss_tea", "loss_distill", "loss_G"}
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline only and the run times exactly --steps steps; --dump-outputs writes
+    what the last timed step returned, and two runs with the same arguments start from the same inputs."""
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("out%d" % k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "32", "--batch", "1", "--steps", "3",
+               "--warmup", "1", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert PLAIN <= set(d), PLAIN - set(d)
+        assert not FULL_ONLY & set(d), FULL_ONLY & set(d)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] > 0 and abs(d["value"] - 1 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+        m = re.search(r"timed region: (\d+) steps in [0-9.]+ s; per-step ms: ([0-9 ]+);", r.stderr.decode())
+        assert m and int(m.group(1)) == 3 and len(m.group(2).split()) == 3, r.stderr.decode()[-2000:]
+        arrays = {f[:-len(".npy")]: np.load(str(out / f)) for f in os.listdir(str(out))}
+        assert set(arrays) == OUTPUTS, sorted(arrays)
+        assert sum(a.nbytes for a in arrays.values()) <= 64e6
+        for name, a in arrays.items():
+            assert a.dtype == np.float32 and np.all(np.isfinite(a)), name
+        assert arrays["pred"].size == 32 ** 3 and arrays["flow"].size == 6 * 32 ** 3  # below the sample size: whole
+        np.testing.assert_allclose(arrays["loss_G"], [d["loss_G"]], rtol=1e-6)
+        runs.append(arrays)
+    # same inputs and weights; the weight gradients' float atomics may reorder sums between runs
+    for name in OUTPUTS:
+        np.testing.assert_allclose(runs[0][name], runs[1][name], rtol=1e-4, atol=1e-4, err_msg=name)

@@ -102,7 +102,7 @@ def _check_two_rank_line(d, backend):
 
 
 def test_bench_starts_its_own_two_ranks_on_one_card():
-    d = _bench(["--gpus", "2", "--size", "32", "--batch", "1", "--steps", "2", "--warmup", "1"],
+    d = _bench(["--gpus", "2", "--size", "32", "--batch", "1", "--steps", "2", "--warmup", "1", "--full"],
                {"FLOWSCI_BENCH_SHARE_GPU": "1"})
     _check_two_rank_line(d, "gloo")
     assert rk_devices(d) == 1
@@ -115,7 +115,7 @@ def rk_devices(d):
 def test_bench_starts_its_own_two_ranks_over_rccl():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (the round-end scaling run covers N > 1 on an 8-GPU node)")
-    d = _bench(["--gpus", "2", "--size", "32", "--batch", "1", "--steps", "2", "--warmup", "1"], {})
+    d = _bench(["--gpus", "2", "--size", "32", "--batch", "1", "--steps", "2", "--warmup", "1", "--full"], {})
     _check_two_rank_line(d, "nccl")
     assert rk_devices(d) == 2
 
