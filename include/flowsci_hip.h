@@ -566,7 +566,8 @@ int fs_conv3d_wrw(const float* g, const float* src, float* dw, int B, int Cg, in
 enum { FS_WRW_KERNEL_BRICK = 0,   /* register-staged position bricks (any shape) */
        FS_WRW_KERNEL_DMA = 1,     /* loader-wave form, direct implicit GEMM */
        FS_WRW_KERNEL_WINO23 = 2,  /* Winograd F(2,3) along x (ablation build only) */
-       FS_WRW_KERNEL_WINO43 = 3   /* Winograd F(4,3) along x: the 64 -> 64 k3 trunk layers */ };
+       FS_WRW_KERNEL_WINO43 = 3,  /* Winograd F(4,3) along x: the 64 -> 64 k3 trunk layers */
+       FS_WRW_KERNEL_S3 = 4       /* loader-wave form on split-bf16 matrix cores: the k = 4 layers with >= 3 source channels */ };
 int fs_conv3d_wrw_kernel_id(const float* g, const float* src, int B, int Cg, int Cs,
                             int Do, int Ho, int Wo, int Di, int Hi, int Wi, int kernel, int stride, int pad);
 

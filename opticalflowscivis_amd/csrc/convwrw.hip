@@ -25,6 +25,10 @@
 // are read from LDS one reduction pair ahead of the MFMAs that use them.  Accumulators stay in
 // registers over the whole run; the epilogue adds the partial tile to dW with float atomics (128
 // contiguous bytes per half-wave = the full-rate shape).
+//
+// Round 6: the k = 4 layers with 3 or more source channels run the loader-wave kernel's bricks on split-bf16 matrix
+// cores instead (convwrw_s3.hpp: fp32 accuracy at the bf16 rate); the fp32-MFMA form stays for the mask head (1-2 source
+// channels) and, in the ablation build, behind FLOWSCI_WRW_NO_S3=1.
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
@@ -69,6 +73,7 @@ struct WB {
   // deterministic mode (fs_conv3d_wrw_det): slab != 0 = floats per private copy of dW; run blockIdx.x STORES its partial
   // tile into copy blockIdx.x of the workspace passed as `dW` (no atomics), wrw_reduce_kernel sums the copies in run order
   long long slab;
+  int ab;            // conv3d_wrw_s3_kernel: measurement switches of the ablation build (FLOWSCI_WRW_S3_AB), else 0
 };
 
 // Deterministic weight gradients: every kernel below splits the positions into runs (blockIdx.x) whose partial tiles
@@ -380,48 +385,41 @@ __device__ unsigned long long fs_wrw_dbg[4 * 8];
 constexpr int up4(int n) { return (n + 3) / 4 * 4; }
 
 // KWX = x extent of a brick (32, or 16 for layers with 16 output columns: a 32-element reduction row is then two
-// consecutive y rows of 16, which are contiguous in G when Wo == 16); TY counts 32-element rows per z slice
-template <int K, int S, int NC, int MT, int TZ, int TY, int FULL, int HALF, int KWX = 32>
-__global__ __launch_bounds__(512, 2) void conv3d_wrw_dma_kernel(const float* __restrict__ G,
-                                                             const float* __restrict__ Src,
-                                                             float* __restrict__ dW, WB p) {
-  constexpr int K3 = K * K * K;
-  constexpr int NTOT = NC * K3;
-  constexpr int NT32 = 4 * FULL + 2 * HALF;
-  static_assert(NT32 * 32 >= NTOT && (NT32 - 1) * 32 < NTOT + 32, "column tiles cover the chunk");
-  static_assert(HALF == 0 || MT == 2, "a shared column tile is split by row tile");
-  constexpr int NB = FULL + HALF;  // B operands per reduction pair
-  constexpr int ROWS = TZ * TY;
+// consecutive y rows of 16, which are contiguous in G when Wo == 16); TY counts 32-element rows per z slice.
+// The LDS images of one brick (shared by the fp32 kernel below and the split-bf16 one of convwrw_s3.hpp).
+template <int K, int S, int NC, int MT, int TZ, int TY, int KWX>
+struct WrwDmaGeom {
   static_assert(KWX == 32 || KWX == 16, "brick x extent");
-  constexpr int YR = KW / KWX;                           // y rows per 32-element reduction row
-  constexpr int TYB = TY * YR;                           // y rows of the brick
-  constexpr int ZT = (TZ - 1) * S + K, YT = (TYB - 1) * S + K;
-  constexpr int XL = 4;                                  // floats between the row start and output column 0's tap 0 + pad
-  constexpr int XP = up4(XL + (KWX - 1) * S + K);        // row pitch = staged row length (the pad shifts taps, not rows)
-  constexpr int PSP = YT * XP, CHSP = ZT * PSP;
-  constexpr int GP = ROWS * KW + 4;
-  constexpr int NGF = 32 * MT * GP;                      // floats of the G image
-  constexpr int NGL = (NGF + 255) / 256 * 256;
-  constexpr int NSF = NC * CHSP;                         // floats of the source image
-  constexpr int NSL = (NSF + 255) / 256 * 256;
-  constexpr int NGW = (NGL / 256 + 3) / 4;               // G pieces (1-KiB wave-instructions) per loader wave
-  constexpr int NSW = (NSL / 256 + 3) / 4;               // source pieces per loader wave
-  constexpr int BUF = NGL + NSL;
+  static constexpr int ROWS = TZ * TY;
+  static constexpr int YR = KW / KWX;                           // y rows per 32-element reduction row
+  static constexpr int TYB = TY * YR;                           // y rows of the brick
+  static constexpr int ZT = (TZ - 1) * S + K, YT = (TYB - 1) * S + K;
+  static constexpr int XL = 4;                                  // floats between the row start and output column 0's tap 0 + pad
+  static constexpr int XP = up4(XL + (KWX - 1) * S + K);        // row pitch = staged row length (the pad shifts taps, not rows)
+  static constexpr int PSP = YT * XP, CHSP = ZT * PSP;
+  static constexpr int GP = ROWS * KW + 4;
+  static constexpr int NGF = 32 * MT * GP;                      // floats of the G image
+  static constexpr int NGL = (NGF + 255) / 256 * 256;
+  static constexpr int NSF = NC * CHSP;                         // floats of the source image
+  static constexpr int NSL = (NSF + 255) / 256 * 256;
+  static constexpr int NGW = (NGL / 256 + 3) / 4;               // G pieces (1-KiB wave-instructions) per loader wave
+  static constexpr int NSW = (NSL / 256 + 3) / 4;               // source pieces per loader wave
+  static constexpr int BUF = NGL + NSL;
   static_assert(2 * BUF * 4 <= 160 * 1024, "two buffers fit the CU's LDS");
-  __shared__ __attribute__((aligned(16))) float lds[2 * BUF];
+};
 
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wv = wave & 3;           // waves 0-3: matrix waves, one per SIMD; waves 4-7: their loader partners
-  const bool loader = wave >= 4;
-  const int l31 = lane & 31, kh = lane >> 5;
+// The loader waves (4-7) of a DMA-staged brick kernel: bricks s0 .. s1 - 1 into the two LDS buffers, one barrier per brick
+template <int K, int S, int NC, int MT, int TZ, int TY, int KWX>
+__device__ __forceinline__ void wrw_dma_loader(const float* __restrict__ G, const float* __restrict__ Src, const WB& p,
+                                               float* lds, int wv, int lane, long long s0, long long s1) {
+  using Geo = WrwDmaGeom<K, S, NC, MT, TZ, TY, KWX>;
+  constexpr int ROWS = Geo::ROWS, YR = Geo::YR, TYB = Geo::TYB, XL = Geo::XL, XP = Geo::XP, PSP = Geo::PSP,
+                CHSP = Geo::CHSP, GP = Geo::GP, NGF = Geo::NGF, NGL = Geo::NGL, NSF = Geo::NSF, NSL = Geo::NSL,
+                NGW = Geo::NGW, NSW = Geo::NSW, BUF = Geo::BUF;
   const int c0 = blockIdx.y * NC;
   const int g0 = blockIdx.z * 32 * MT;
   const size_t gvol = (size_t)p.Do * p.Ho * p.Wo, svol = (size_t)p.Di * p.Hi * p.Wi;
-  const long long s0 = (long long)blockIdx.x * p.spw;
-  const long long s1 = min(s0 + p.spw, p.bricks);
-
-  if (loader) {
+  {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the host pass has neither the buffer-resource type nor the LDS-DMA builtin)
     __builtin_amdgcn_s_setprio(3);  // (a loader wave issues a handful of instructions per period: they should not queue behind the matrix wave's)
     // ---- brick-invariant part of the staging.  Piece k of loader wave wv fills the 16-byte slots
@@ -536,8 +534,40 @@ __global__ __launch_bounds__(512, 2) void conv3d_wrw_dma_kernel(const float* __r
       buf ^= 1;
     }
 #else
-    (void)gvol; (void)svol; (void)NGW; (void)NSW; (void)DMA_OOB;
+    (void)G; (void)Src; (void)p; (void)lds; (void)wv; (void)lane; (void)s0; (void)s1; (void)c0; (void)g0; (void)gvol; (void)svol;
+    (void)ROWS; (void)YR; (void)TYB; (void)XL; (void)XP; (void)PSP; (void)CHSP; (void)GP; (void)NGF; (void)NGL; (void)NSF;
+    (void)NSL; (void)NGW; (void)NSW; (void)BUF; (void)DMA_OOB;
 #endif
+  }
+}
+
+template <int K, int S, int NC, int MT, int TZ, int TY, int FULL, int HALF, int KWX = 32>
+__global__ __launch_bounds__(512, 2) void conv3d_wrw_dma_kernel(const float* __restrict__ G,
+                                                             const float* __restrict__ Src,
+                                                             float* __restrict__ dW, WB p) {
+  constexpr int K3 = K * K * K;
+  constexpr int NTOT = NC * K3;
+  constexpr int NT32 = 4 * FULL + 2 * HALF;
+  static_assert(NT32 * 32 >= NTOT && (NT32 - 1) * 32 < NTOT + 32, "column tiles cover the chunk");
+  static_assert(HALF == 0 || MT == 2, "a shared column tile is split by row tile");
+  constexpr int NB = FULL + HALF;  // B operands per reduction pair
+  using Geo = WrwDmaGeom<K, S, NC, MT, TZ, TY, KWX>;
+  constexpr int ROWS = Geo::ROWS, YR = Geo::YR, XL = Geo::XL, XP = Geo::XP, PSP = Geo::PSP, CHSP = Geo::CHSP,
+                GP = Geo::GP, NGL = Geo::NGL, BUF = Geo::BUF;
+  __shared__ __attribute__((aligned(16))) float lds[2 * BUF];
+
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wv = wave & 3;           // waves 0-3: matrix waves, one per SIMD; waves 4-7: their loader partners
+  const bool loader = wave >= 4;
+  const int l31 = lane & 31, kh = lane >> 5;
+  const int c0 = blockIdx.y * NC;
+  const int g0 = blockIdx.z * 32 * MT;
+  const long long s0 = (long long)blockIdx.x * p.spw;
+  const long long s1 = min(s0 + p.spw, p.bricks);
+
+  if (loader) {
+    wrw_dma_loader<K, S, NC, MT, TZ, TY, KWX>(G, Src, p, lds, wv, lane, s0, s1);
     return;
   }
 
@@ -673,6 +703,7 @@ int launch_dma(const float* G, const float* Src, float* dW, const WP& w, hipStre
 
 #include "convwrwwino.hpp"
 #include "convwrwwino4.hpp"
+#include "convwrw_s3.hpp"
 
 }  // namespace
 
@@ -730,8 +761,14 @@ static int conv3d_wrw_impl(const float* g, const float* src, const float* const*
                       (((uintptr_t)g | (srcv ? (uintptr_t)0 : (uintptr_t)src)) & 15) == 0 && ms_aligned &&
                       (long long)64 * Do * Ho * Wo * 4 < (1ll << 31) && (long long)16 * Di * Hi * Wi * 4 < (1ll << 31);
   // per-channel planes: only the loader-wave kernel of IFBlock's conv0[0] (k = 4, <= 32 gradient channels)
+  // k = 4 with 3 or more source channels: the split-bf16 form of the loader-wave kernel (convwrw_s3.hpp); `FLOWSCI_WRW_NO_S3=1`
+  // (ablation build): the fp32-MFMA kernel of the same bricks
+  static const bool no_s3 = FS_AB_ENV("FLOWSCI_WRW_NO_S3");
   if (srcv != nullptr) {
-    if (dma_ok && kernel == 4 && Cg <= 32 && Cs >= 3 && Wo >= KW) FS_WRW_PICK(FS_WRW_KERNEL_DMA, launch_dma<4, 2, 6, 1, 2, 2, 3, 0>(g, src, dw, p, st, det));
+    if (dma_ok && kernel == 4 && Cg <= 32 && Cs >= 3 && Wo >= KW) {
+      if (!no_s3) FS_WRW_PICK(FS_WRW_KERNEL_S3, launch_wrw_s3<6, 1, 2, 2, 3, 0>(g, src, dw, p, st, det));
+      FS_WRW_PICK(FS_WRW_KERNEL_DMA, launch_dma<4, 2, 6, 1, 2, 2, 3, 0>(g, src, dw, p, st, det));
+    }
     return FS_ERR_UNSUPPORTED;
   }
   // the 64 -> 64 k3 layers of the 64^3 trunk: the Winograd F(4,3) form (convwrwwino4.hpp), or F(2,3) (convwrwwino.hpp)
@@ -742,6 +779,11 @@ static int conv3d_wrw_impl(const float* g, const float* src, const float* const*
   if (dma_ok) {
     if (kernel == 3 && Cg > 32 && Cs >= 8 && Wo == 16) FS_WRW_PICK(FS_WRW_KERNEL_DMA, launch_dma<3, 1, 16, 2, 1, 4, 3, 1, 16>(g, src, dw, p, st, det));
     if (kernel == 3 && Cg > 32 && Cs >= 8) FS_WRW_PICK(FS_WRW_KERNEL_DMA, launch_dma<3, 1, 16, 2, 1, 4, 3, 1>(g, src, dw, p, st, det));
+    if (!no_s3) {
+      if (kernel == 4 && Cg > 32 && Cs >= 4 && Wo == 16) FS_WRW_PICK(FS_WRW_KERNEL_S3, launch_wrw_s3<8, 2, 1, 2, 4, 0, 16>(g, src, dw, p, st, det));
+      if (kernel == 4 && Cg > 32 && Cs >= 4 && Wo >= KW) FS_WRW_PICK(FS_WRW_KERNEL_S3, launch_wrw_s3<8, 2, 1, 2, 4, 0>(g, src, dw, p, st, det));
+      if (kernel == 4 && Cg <= 32 && Cs >= 3 && Wo >= KW) FS_WRW_PICK(FS_WRW_KERNEL_S3, launch_wrw_s3<6, 1, 2, 2, 3, 0>(g, src, dw, p, st, det));
+    }
     if (kernel == 4 && Cg > 32 && Cs >= 4 && Wo == 16) FS_WRW_PICK(FS_WRW_KERNEL_DMA, launch_dma<4, 2, 8, 2, 1, 2, 4, 0, 16>(g, src, dw, p, st, det));
     if (kernel == 4 && Cg > 32 && Cs >= 4 && Wo >= KW) FS_WRW_PICK(FS_WRW_KERNEL_DMA, launch_dma<4, 2, 8, 2, 1, 2, 4, 0>(g, src, dw, p, st, det));
     if (kernel == 4 && Cg <= 32 && Cs >= 3 && Wo >= KW) FS_WRW_PICK(FS_WRW_KERNEL_DMA, launch_dma<4, 2, 6, 1, 2, 2, 3, 0>(g, src, dw, p, st, det));

@@ -1776,7 +1776,7 @@ def _dw_zeros(like, shape):
     return out
 
 
-def _conv3d_wrw_det(g, src_ptr, pv, sv, geo, nbytes, flops, equiv, allow_unsupported=False):
+def _conv3d_wrw_det(g, src_ptr, pv, sv, geo, nbytes, flops, equiv, allow_unsupported=False, kernel=None):
     """fs_conv3d_wrw_det: the same kernels with every run of positions storing its partial tile into its own copy of dW
     (a workspace of runs x |dW| floats) and one more launch adding the copies in run order -- no float atomics, bitwise
     reproducible.  Taken when torch.are_deterministic_algorithms_enabled()."""
@@ -1792,7 +1792,7 @@ def _conv3d_wrw_det(g, src_ptr, pv, sv, geo, nbytes, flops, equiv, allow_unsuppo
     ws = g.new_empty(max(need, 1))
     with torch.cuda.device(g.device):
         _call("fs_conv3d_wrw_det", g.data_ptr(), src_ptr, pv, sv, dw.data_ptr(), ws.data_ptr(), need, *geo, _stream(g),
-              algo_bytes=nbytes, algo_flops=flops, equiv_flops=equiv, record_as="fs_conv3d_wrw")
+              algo_bytes=nbytes, algo_flops=flops, equiv_flops=equiv, record_as="fs_conv3d_wrw", kernel=kernel)
     return dw
 
 
@@ -1807,20 +1807,31 @@ def conv3d_wrw(g, src, k, stride, pad):
     fq = 2 * g.numel() * Cs * int(k) ** 3
     kid = conv3d_wrw_kernel_id(g.data_ptr(), src.data_ptr(), B, Cg, Cs, g.shape[2:], src.shape[2:], k, stride, pad)
     geo = (B, Cg, Cs, g.shape[2], g.shape[3], g.shape[4], src.shape[2], src.shape[3], src.shape[4], int(k), int(stride), int(pad))
+    fl = {WRW_KERNEL_WINO43: fq // 2, WRW_KERNEL_WINO23: fq * 2 // 3, WRW_KERNEL_S3: 6 * fq}.get(kid, fq)
     if torch.are_deterministic_algorithms_enabled():
-        return _conv3d_wrw_det(g, src.data_ptr(), None, None, geo, 4 * (g.numel() + src.numel()),
-                               {WRW_KERNEL_WINO43: fq // 2, WRW_KERNEL_WINO23: fq * 2 // 3}.get(kid, fq), fq)
+        return _conv3d_wrw_det(g, src.data_ptr(), None, None, geo, 4 * (g.numel() + src.numel()), fl, fq,
+                               kernel=_wrw_s3_symbol(kid, Cg, g.shape[4]))
     dw = _dw_zeros(g, (Cg, Cs, k, k, k))
     with torch.cuda.device(g.device):
         _call("fs_conv3d_wrw", g.data_ptr(), src.data_ptr(), dw.data_ptr(), B, Cg, Cs, g.shape[2],
               g.shape[3], g.shape[4], src.shape[2], src.shape[3], src.shape[4], int(k), int(stride),
               int(pad), _stream(g), algo_bytes=4 * (g.numel() + src.numel()),
-              algo_flops={WRW_KERNEL_WINO43: fq // 2, WRW_KERNEL_WINO23: fq * 2 // 3}.get(kid, fq), equiv_flops=fq,
-              kernel="conv3d_wrw_wino4_kernel<0>" if kid == WRW_KERNEL_WINO43 else None)
+              algo_flops=fl, equiv_flops=fq,
+              kernel="conv3d_wrw_wino4_kernel<0>" if kid == WRW_KERNEL_WINO43 else _wrw_s3_symbol(kid, Cg, g.shape[4]))
     return dw
 
 
-WRW_KERNEL_BRICK, WRW_KERNEL_DMA, WRW_KERNEL_WINO23, WRW_KERNEL_WINO43 = 0, 1, 2, 3  # include/flowsci_hip.h FS_WRW_KERNEL_*
+def _wrw_s3_symbol(kid, Cg, Wo):
+    """Kernel symbol of a weight-gradient call that runs on split-bf16 matrix cores (csrc/convwrw_s3.hpp): its launch
+    records carry the EXECUTED flops (six bf16 products per fp32 multiply-add), priced against the bf16 peak; else None."""
+    if kid != WRW_KERNEL_S3:
+        return None
+    if int(Cg) > 32:
+        return "conv3d_wrw_s3_kernel<8, 2, 1, 2, 4, 0, %d>" % (16 if int(Wo) == 16 else 32)
+    return "conv3d_wrw_s3_kernel<6, 1, 2, 2, 3, 0, 32>"
+
+
+WRW_KERNEL_BRICK, WRW_KERNEL_DMA, WRW_KERNEL_WINO23, WRW_KERNEL_WINO43, WRW_KERNEL_S3 = 0, 1, 2, 3, 4  # include/flowsci_hip.h FS_WRW_KERNEL_*
 
 
 def conv3d_wrw_kernel_id(g_ptr, src_ptr, B, Cg, Cs, g_dhw, src_dhw, k, stride, pad):
@@ -1913,15 +1924,20 @@ def conv3d_wrw_ms(g, pieces, k, stride, pad):
     g = _need_cuda_f32("g", g, 5)
     B, Cg = g.shape[:2]
     Di, Hi, Wi = pieces[0].shape[2:]
+    fq = 2 * g.numel() * Cs * int(k) ** 3
+    # (the multi-source dispatch is the single-tensor one's for the same shape; the first plane stands for the alignment)
+    kid = conv3d_wrw_kernel_id(g.data_ptr(), pieces[0].data_ptr(), B, Cg, Cs, g.shape[2:], (Di, Hi, Wi), k, stride, pad)
+    sym = _wrw_s3_symbol(kid, Cg, g.shape[4])
+    fl = 6 * fq if sym is not None else fq
     if torch.are_deterministic_algorithms_enabled():
         geo = (B, Cg, Cs, g.shape[2], g.shape[3], g.shape[4], Di, Hi, Wi, int(k), int(stride), int(pad))
-        fq = 2 * g.numel() * Cs * int(k) ** 3
-        return _conv3d_wrw_det(g, 0, pv, sv, geo, 4 * (g.numel() + B * Cs * Di * Hi * Wi), fq, fq, allow_unsupported=True)
+        return _conv3d_wrw_det(g, 0, pv, sv, geo, 4 * (g.numel() + B * Cs * Di * Hi * Wi), fl, fq, allow_unsupported=True,
+                               kernel=sym)
     dw = _dw_zeros(g, (Cg, Cs, k, k, k))
     with torch.cuda.device(g.device):
         rc = _call_rc("fs_conv3d_wrw_ms", g.data_ptr(), pv, sv, dw.data_ptr(), B, Cg, Cs, g.shape[2], g.shape[3], g.shape[4],
                    Di, Hi, Wi, int(k), int(stride), int(pad), _stream(g),
-                      algo_bytes=4 * (g.numel() + B * Cs * Di * Hi * Wi), algo_flops=2 * g.numel() * Cs * int(k) ** 3,
+                      algo_bytes=4 * (g.numel() + B * Cs * Di * Hi * Wi), algo_flops=fl, equiv_flops=fq, kernel=sym,
                       record_as="fs_conv3d_wrw", allow=(FS_ERR_UNSUPPORTED,))
     if rc == FS_ERR_UNSUPPORTED:
         return None
