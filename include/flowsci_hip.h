@@ -43,8 +43,9 @@ enum {
  *   320  round 4: fs_conv3d_wrw_kernel_id (which weight-gradient kernel a call dispatches to; nothing launched);
  *        fs_conv3d_wrw_det / fs_conv3d_wrw_det_ws_floats (workspace form without float atomics).
  *        The library reads no environment variable any more (measurement switches live in the -DFS_ABLATION build).
- *   330  round 5: fs_warp3d_kernel_id (which kernel a trilinear-warp call dispatches to; nothing launched). */
-#define FS_ABI_VERSION 330
+ *   330  round 5: fs_warp3d_kernel_id (which kernel a trilinear-warp call dispatches to; nothing launched).
+ *   340  fs_frame_metrics2d / fs_frame_metrics3d and their _ws_bytes queries (sequence evaluation: PSNR / SSIM). */
+#define FS_ABI_VERSION 340
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -628,6 +629,31 @@ int fs_conv3d_fwd_wprep_jobs(FsWprepJob* jobs_host, int cap, const float* x, con
 int fs_conv3d_tr_wprep_jobs(FsWprepJob* jobs_host, int cap, const float* x, const float* w, float* ws, int B, int Cin,
                             int Cout, int Di, int Hi, int Wi, int Dout, int Hout, int Wout, int has_prelu_out);
 int fs_conv3d_wprep_batch(const FsWprepJob* jobs_dev, int njobs, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Sequence evaluation metrics -- error.py:27-56 calculate_psnr / ssim, per frame, N frames per launch.
+ *   x, y [N,C,H,W] (2-D) or [N,C,D,H,W] (3-D), fp32, any value range L (`L` = data range: 255 for the reference's
+ *   bytes, 1 for [0,1] data).  For every frame n:
+ *     out_sse[n]      = sum over all C*H*W (C*D*H*W) elements of (x - y)^2                       (fp64)
+ *     out_ssim_sum[n] = sum over the C channels and the VALID region of the SSIM map             (fp64)
+ *   SSIM map: separable 11-tap Gaussian window g = cv2.getGaussianKernel(11, 1.5) along each axis, valid region
+ *   (H-10) x (W-10) (2-D) or (D-10)(H-10)(W-10) (3-D), sigma^2 = E[x^2] - mu^2, C1 = (0.01 L)^2, C2 = (0.03 L)^2,
+ *   ssim = ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sxx + syy + C2)).  PSNR = 10 log10(L^2 / mse) with
+ *   mse = out_sse / (C*H*W), the mean SSIM = out_ssim_sum / (C * valid region); for C = 3 the mean over channels is
+ *   what error.py:68-72 returns.  The reference has no working 3-D form (calculate_ssim returns None for volumes,
+ *   error.py:67-74): the 3-D window is the same construction along a third axis, pinned by this project's fp64
+ *   restatement only.
+ *   fp32 inputs, fp64 window sums, fp64 partials per workgroup in `ws` (fs_frame_metrics{2,3}d_ws_bytes bytes, 8-byte aligned),
+ *   summed by a second launch in a fixed order: bitwise reproducible, no atomics.
+ *   FS_ERR_SHAPE: N or C < 1, a filtered extent below 11, or a grid beyond 2^24 workgroups; FS_ERR_ARG: L <= 0.
+ *   The _ws_bytes queries launch nothing and return the byte count or -(FS_ERR_*).
+ */
+long long fs_frame_metrics2d_ws_bytes(int N, int C, int H, int W);
+long long fs_frame_metrics3d_ws_bytes(int N, int C, int D, int H, int W);
+int fs_frame_metrics2d(const float* x, const float* y, int N, int C, int H, int W, double L, double* ws,
+                       double* out_sse, double* out_ssim_sum, fs_stream_t stream);
+int fs_frame_metrics3d(const float* x, const float* y, int N, int C, int D, int H, int W, double L, double* ws,
+                       double* out_sse, double* out_ssim_sum, fs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -109,6 +109,71 @@ def vortex2d_pairs(B, H=150, W=450, seed=0, device="cpu", nvort=8, max_shift=3.0
     return out
 
 
+# ---- whole sequences (sequence evaluation, opticalflowscivis_amd.evaluate): the motion models of the triplet generators
+# above evaluated at t = 0 .. T-1.  The triplet generators stay as they are (fixtures and pins depend on their draws).
+
+def _seq_start(g, T, S, r, v):
+    """Start centre per axis so that the whole trajectory c0 + v t, t in [0, T-1], keeps the object inside [0, S)."""
+    lo = r + 1 + torch.clamp(-v * (T - 1), min=0)
+    hi = S - 1 - r - torch.clamp(v * (T - 1), min=0)
+    u = torch.rand(v.shape, generator=g)
+    return torch.where(hi > lo, lo + u * (hi - lo), (lo + hi) / 2)
+
+
+def droplet3d_sequence(T, S, seed=1234, device="cpu", radius=(40, 80), max_shift=1.0):
+    """[T,S,S,S]: the binary sphere of droplet3d_batch translating by <= max_shift voxels per frame, frames t = 0..T-1
+    (radius range given for S=256, scaled with S)."""
+    g = _gen(seed, device)
+    r = float(torch.rand(1, generator=g) * (radius[1] - radius[0]) + radius[0]) * S / 256.0
+    v = (torch.rand(3, generator=g) * 2 - 1) * max_shift
+    c0 = _seq_start(g, T, S, r, v)
+    ax = torch.arange(S, dtype=torch.float32, device=device)
+    out = torch.empty(T, S, S, S, dtype=torch.float32, device=device)
+    for t in range(T):
+        c = (c0 + v * t).to(device)
+        d2 = ((ax - c[0]) ** 2).view(S, 1, 1) + ((ax - c[1]) ** 2).view(1, S, 1) + ((ax - c[2]) ** 2).view(1, 1, S)
+        out[t] = (d2 <= r * r).float()
+    return out
+
+
+def jets3d_sequence(T, S, seed=1234, device="cpu", njets=5, max_shift=1.0):
+    """[T,S,S,S]: the Gaussian plumes of jets3d_batch advected by <= max_shift voxels per frame, frames t = 0..T-1,
+    min-max normalised to [0,1] over the whole sequence."""
+    g = _gen(seed, device)
+    ax = torch.linspace(0, 1, S, device=device)
+    cen = torch.rand(njets, 3, generator=g) * 0.6 + 0.2
+    sig = torch.rand(njets, 3, generator=g) * 0.08 + 0.04
+    vel = (torch.rand(njets, 3, generator=g) * 2 - 1) * max_shift / S
+    out = torch.zeros(T, S, S, S, dtype=torch.float32, device=device)
+    for t in range(T):
+        for j in range(njets):
+            c = cen[j] + vel[j] * t
+            e = ((ax - float(c[0])) / float(sig[j, 0])).pow(2).view(S, 1, 1) + \
+                ((ax - float(c[1])) / float(sig[j, 1])).pow(2).view(1, S, 1) + \
+                ((ax - float(c[2])) / float(sig[j, 2])).pow(2).view(1, 1, S)
+            out[t] += torch.exp(-0.5 * e)
+    lo, hi = out.min(), out.max()
+    return (out - lo) / (hi - lo + 1e-12)
+
+
+def droplet2d_sequence(T, H=160, W=224, seed=1234, device="cpu", radius=(20, 40), max_shift=2.0):
+    """[T,H,W]: the blurred disc of droplet2d_batch translating by <= max_shift px per frame, frames t = 0..T-1."""
+    g = _gen(seed, device)
+    r = float(torch.rand(1, generator=g) * (radius[1] - radius[0]) + radius[0])
+    v = (torch.rand(2, generator=g) * 2 - 1) * max_shift  # (vy, vx)
+    c0 = _seq_start(g, T, torch.tensor([float(H), float(W)]), r, v)
+    ys = torch.arange(H, dtype=torch.float32, device=device).view(H, 1)
+    xs = torch.arange(W, dtype=torch.float32, device=device).view(1, W)
+    k = torch.exp(-0.5 * (torch.arange(-3, 4, dtype=torch.float32, device=device)) ** 2)
+    k = k / k.sum()
+    out = torch.empty(T, 1, H, W, dtype=torch.float32, device=device)
+    for t in range(T):
+        d2 = (ys - float(c0[0] + v[0] * t)) ** 2 + (xs - float(c0[1] + v[1] * t)) ** 2
+        out[t, 0] = (d2 <= r * r).float()
+    out = torch.nn.functional.conv2d(torch.nn.functional.pad(out, (3, 3, 0, 0), mode="replicate"), k.view(1, 1, 1, 7))
+    out = torch.nn.functional.conv2d(torch.nn.functional.pad(out, (0, 0, 3, 3), mode="replicate"), k.view(1, 1, 7, 1))
+    return out.view(T, H, W).clamp(0, 1)
+
 def psnr(pred, gt):
     """PSNR on [0,1] data: -10 log10(mean((pred-gt)^2)) (Flow-3D/train.py:385)."""
     mse = torch.mean((pred.double() - gt.double()) ** 2)

@@ -1,7 +1,8 @@
 """Drop-in for Flow-3D/inference_img.py: interpolate 2**exp - 1 frames between two inputs by
 recursive bisection (inference_img.py:88-97).  Inputs / outputs are .npy arrays in [0,1]
 (the reference reads PNG/EXR through cv2, which this image does not have); spatial sizes are padded
-to a multiple of 32 like the reference (:56-61)."""
+to a multiple of 32 like the reference (:56-61).  --ratio r (0 < r < 1) writes img0, the frame at r found by bisection
+(:64-87, --rthreshold, --rmaxcycles) and img1 as img0.npy, img1.npy, img2.npy."""
 import argparse
 import os
 
@@ -9,6 +10,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ..evaluate import ratio_inference
 from .model.RIFE import Model
 
 ND = 3
@@ -20,6 +22,11 @@ def main():
     ap.add_argument('--exp', default=1, type=int)
     ap.add_argument('--model', default='train_log', help='directory holding flownet.pkl')
     ap.add_argument('--out', default='output')
+    ap.add_argument('--ratio', default=0, type=float, help='inference ratio between the two inputs in 0 - 1 '
+                    '(0: --exp bisection levels instead)')
+    ap.add_argument('--rthreshold', default=0.02, type=float,
+                    help='return the frame whose ratio falls within this range of --ratio')
+    ap.add_argument('--rmaxcycles', default=8, type=int, help='limit of bisection cycles')
     args = ap.parse_args()
     dev = torch.device('cuda')
     model = Model(-1, device=dev)
@@ -37,7 +44,9 @@ def main():
     a, b = F.pad(a, pad), F.pad(b, pad)
     frames = [a, b]
     with torch.no_grad():
-        for _ in range(args.exp):
+        if args.ratio:
+            frames = [a, ratio_inference(model, a, b, args.ratio, args.rthreshold, args.rmaxcycles), b]
+        for _ in range(0 if args.ratio else args.exp):
             nxt = []
             for x, y in zip(frames[:-1], frames[1:]):
                 mid = model.inference(x, y)[0]

@@ -2218,3 +2218,80 @@ class _WSSIMLoss(torch.autograd.Function):
 def weighted_ssim_loss(x, y, occ_mask, photo_loss_use_occ):
     """photo_loss_multi_type(..., photo_loss_type='SSIM') in one fused pass."""
     return _WSSIMLoss.apply(x, y, occ_mask, bool(photo_loss_use_occ))
+
+
+# --------------------------------------------------------------------------------------------
+# Sequence evaluation: error.py:27-56 calculate_psnr / ssim per frame (fs_frame_metrics{2,3}d)
+# --------------------------------------------------------------------------------------------
+def frame_metrics_cost(shape, window="2d"):
+    """(HBM bytes, flops) the algorithm needs for one frame_metrics call on [N,C,*spatial] inputs: both inputs
+    read once; per element of the SSIM region 3 products, the five maps filtered with 11 taps along each axis (2 flops
+    a tap) and ~15 flops of SSIM formula; per element 3 flops of squared error."""
+    nd = 2 if window == "2d" else 3
+    n = 1
+    for s in shape:
+        n *= int(s)
+    lead = int(shape[0]) * int(shape[1])
+    valid = lead
+    for s in shape[2:]:
+        valid *= int(s) - 10
+    return 2 * 4 * n, 3 * n + valid * (3 + 5 * 11 * 2 * nd + 15)
+
+
+def frame_metrics(pred, gt, data_range=1.0, window="2d"):
+    """Per-frame PSNR and SSIM of `pred` against `gt` -- error.py:27-56 (calculate_psnr, ssim) for N frames in one
+    launch.  window="2d": [N,C,H,W] (or [N,H,W]), the reference's 11x11 Gaussian SSIM, mean over the C channels' maps;
+    window="3d": [N,C,D,H,W] (or [N,D,H,W]), the same window along three axes (no reference form exists: pinned by the
+    project's fp64 restatement).  The window sums are fp64 inside the kernel (fp32 sums of E[x^2] - mu^2 lose ~1e-5 of
+    SSIM on flat regions), the result within ~1e-7 of an fp64 evaluation.  Every filtered extent must be >= 11.  Inputs of another dtype are converted to fp32,
+    non-contiguous ones copied once.  Returns (psnr [N], ssim [N]) as fp64 tensors on the inputs' device;
+    psnr = 10 log10(L^2 / mse), +inf where mse == 0 (error.py:31-33), L = data_range."""
+    if window not in ("2d", "3d"):
+        raise ValueError("window must be '2d' or '3d', got %r" % (window,))
+    nd = 2 if window == "2d" else 3
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a tensor" % name)
+        if not t.is_cuda:
+            raise ValueError("%s must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (name, t.device))
+        if t.dim() not in (nd + 1, nd + 2):
+            raise ValueError("%s must be [N,C,%s] or [N,%s] for window=%r, got shape %s" %
+                             (name, ",".join("DHW"[3 - nd:]), ",".join("DHW"[3 - nd:]), window, tuple(t.shape)))
+    if pred.shape != gt.shape:
+        raise ValueError("pred and gt differ in shape: %s vs %s" % (tuple(pred.shape), tuple(gt.shape)))
+    if pred.device != gt.device:
+        raise ValueError("pred and gt are on different devices")
+    if not float(data_range) > 0:
+        raise ValueError("data_range must be > 0, got %r" % (data_range,))
+    if pred.dim() == nd + 1:
+        pred, gt = pred.unsqueeze(1), gt.unsqueeze(1)
+    if any(s < 11 for s in pred.shape[2:]):
+        raise ValueError("every filtered extent must be >= 11 (11-tap valid window), got %s" % (tuple(pred.shape),))
+    x = pred.to(torch.float32).contiguous()
+    y = gt.to(torch.float32).contiguous()
+    N, C = x.shape[:2]
+    sp = tuple(x.shape[2:])
+    if N == 0:
+        e = torch.empty(0, dtype=torch.float64, device=x.device)
+        return e, e.clone()
+    lib = _lib.lib()
+    nb = (lib.fs_frame_metrics2d_ws_bytes(N, C, *sp) if nd == 2 else lib.fs_frame_metrics3d_ws_bytes(N, C, *sp))
+    if nb < 0:
+        _lib.check(int(-nb), "fs_frame_metrics%dd_ws_bytes" % nd)
+    ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=x.device)
+    sums = torch.empty(2, N, dtype=torch.float64, device=x.device)
+    nbytes, flops = frame_metrics_cost(x.shape, window)
+    name = "fs_frame_metrics%dd" % nd
+    with torch.cuda.device(x.device):
+        _call(name, x.data_ptr(), y.data_ptr(), N, C, *sp, float(data_range), ws.data_ptr(), sums[0].data_ptr(),
+              sums[1].data_ptr(), _stream(x), algo_bytes=nbytes, algo_flops=flops)
+    L = float(data_range)
+    per = C
+    for s in sp:
+        per *= s
+    valid = C
+    for s in sp:
+        valid *= s - 10
+    mse = sums[0] / per
+    psnr = 10.0 * torch.log10((L * L) / mse)  # mse == 0 -> L^2/0 = inf -> +inf
+    return psnr, sums[1] / valid
