@@ -44,8 +44,9 @@ enum {
  *        fs_conv3d_wrw_det / fs_conv3d_wrw_det_ws_floats (workspace form without float atomics).
  *        The library reads no environment variable any more (measurement switches live in the -DFS_ABLATION build).
  *   330  round 5: fs_warp3d_kernel_id (which kernel a trilinear-warp call dispatches to; nothing launched).
- *   340  fs_frame_metrics2d / fs_frame_metrics3d and their _ws_bytes queries (sequence evaluation: PSNR / SSIM). */
-#define FS_ABI_VERSION 340
+ *   340  fs_frame_metrics2d / fs_frame_metrics3d and their _ws_bytes queries (sequence evaluation: PSNR / SSIM).
+ *   350  fs_flow_metrics2d / fs_flow_metrics3d and their _ws_bytes queries (flow accuracy: EPE, Fl, angular error). */
+#define FS_ABI_VERSION 350
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -654,6 +655,48 @@ int fs_frame_metrics2d(const float* x, const float* y, int N, int C, int H, int 
                        double* out_sse, double* out_ssim_sum, fs_stream_t stream);
 int fs_frame_metrics3d(const float* x, const float* y, int N, int C, int D, int H, int W, double L, double* ws,
                        double* out_sse, double* out_ssim_sum, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Flow accuracy -- end-point error, RMSE, angular error and the KITTI outlier rate Fl of N predicted flows against N
+ * ground-truth displacements, one launch.
+ *   pred, gt: N flows of C fp32 planes of D*H*W (2-D: D = 1, C = 2; 3-D: C = 3) elements each; the planes of one flow
+ *     are contiguous ([C, D, H, W]), flow n starts at pred + n * pred_bstride (gt + n * gt_bstride) elements, so the
+ *     channel slice flow[:, C:2C] of an [N, 2C, ...] tensor is passed without a copy (bstride >= C*D*H*W when N > 1).
+ *     Channel 0 is the displacement along W, 1 along H, 2 along D, in elements.
+ *   valid, noc: uint8 [N, D, H, W] (contiguous, nonzero = set) or NULL.  valid NULL: every element is valid.  noc NULL:
+ *     no occlusion split (the noc sums stay 0).  noc only counts where valid is set.
+ *   convention (3-D only): FS_FLOW_DISP, or FS_FLOW_RIFE3D: pred is a Flow-3D (rife3d) flow, whose warp rotates axes
+ *     (out[d,h,w] samples the input at ix = (h+F0)(W-1)/(H-1), iy = (d+F1)(H-1)/(D-1), iz = (w+F2)(D-1)/(W-1)); the
+ *     kernel converts it to the displacement x = ix - w, y = iy - h, z = iz - d (fp64, not clamped) first.  gt is
+ *     always a displacement.  RIFE3D needs D, H, W >= 2 (FS_ERR_SHAPE).
+ *   Per element: e2 = |p - g|^2 and epe = sqrt(e2) in fp64; ae = atan2(|a x b|, a.b) with a = (p, 1), b = (g, 1), its
+ *     arguments in fp64 and the atan2 in fp32 (radians); outlier = e2 > tau_abs^2 && e2 > tau_rel^2 |g|^2 (fp64; KITTI
+ *     Fl: epe > 3 px and > 5 % of |g|).  An element whose pred or gt has a non-finite component counts in n, in
+ *     n_outlier and in n_nonfinite, and in none of the sums or the max.
+ *   epe_map: fp32 [N, D, H, W] (contiguous) or NULL: epe at EVERY element, valid or not; NaN where pred or gt is not
+ *     finite.
+ *   out: fp64 [N][FS_FLOW_METRICS_K], per flow, in this order (the noc entries over valid AND noc):
+ *     0 n_valid   1 sum epe   2 sum epe^2   3 sum ae   4 n_outlier   5 max epe (-inf when no finite valid element)
+ *     6 n_noc     7 sum epe   8 sum epe^2   9 sum ae  10 n_outlier
+ *    11 n_nonfinite (valid)  12 n_nonfinite (valid and noc)
+ *     Means are over the finite elements (n - n_nonfinite), Fl = n_outlier / n; occluded = valid minus noc.
+ *   Per-workgroup fp64 partials in `ws` (fs_flow_metrics{2,3}d_ws_bytes bytes, 8-byte aligned), summed by a second
+ *   launch in a fixed order: bitwise reproducible, no atomics.
+ *   FS_ERR_SHAPE: N < 1, C other than 2 (2-D) / 3 (3-D), an extent < 1 (< 2 under RIFE3D), a batch stride below
+ *   C*D*H*W; FS_ERR_ARG: an unknown convention, tau_abs or tau_rel negative or not finite.
+ *   The _ws_bytes queries launch nothing and return the byte count or -(FS_ERR_*).
+ */
+#define FS_FLOW_METRICS_K 13
+#define FS_FM_MAX_EPE 5
+enum { FS_FLOW_DISP = 0, FS_FLOW_RIFE3D = 1 };
+long long fs_flow_metrics2d_ws_bytes(int N, int C, int H, int W);
+long long fs_flow_metrics3d_ws_bytes(int N, int C, int D, int H, int W, int convention);
+int fs_flow_metrics2d(const float* pred, const float* gt, int N, int C, int H, int W, long long pred_bstride,
+                      long long gt_bstride, const unsigned char* valid, const unsigned char* noc, float tau_abs,
+                      float tau_rel, float* epe_map, double* ws, double* out, fs_stream_t stream);
+int fs_flow_metrics3d(const float* pred, const float* gt, int N, int C, int D, int H, int W, long long pred_bstride,
+                      long long gt_bstride, const unsigned char* valid, const unsigned char* noc, int convention,
+                      float tau_abs, float tau_rel, float* epe_map, double* ws, double* out, fs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,253 @@
+"""Flow evaluation: score the flows a model estimates on a time series against the known motion (ops.flow_metrics:
+EPE, EPE noc / occ, RMSE, angular error, Fl).  Shared by the flow2d / flow3d `evaluate_flow` and the upflow `test`
+entry points:
+
+    python -m opticalflowscivis_amd.flow3d.evaluate_flow --dataset jets3d --size 64 --frames 9 --gap 2 --zero-baseline
+    python -m opticalflowscivis_amd.flow2d.evaluate_flow --dataset droplet2d --gap 2 --out r.json
+    python -m opticalflowscivis_amd.upflow.test --dataset rectangle2d --gap 1 --save-flows flows/
+
+RIFE models (flow2d, flow3d) interpolate the mid frame of each pair (t, t+g), g even: their final flow holds
+F_mid->0 = flow[:, :C], scored against gt(mid, t), and F_mid->1 = flow[:, C:2C], scored against gt(mid, t+g).  The
+Flow-3D flow is not a displacement (its warp rotates axes): it is converted with ops.rife3d_to_disp at the padded
+extents the model ran on, then cropped and scored as a displacement (--save-flows writes that displacement).  UPFlow's
+flow_f_out is scored against gt(t, t+g) and flow_b_out against gt(t+g, t).  Every flow of one sequence goes through
+one flow_metrics launch.
+
+--seq takes a [T,H,W] (2-D) or [T,D,H,W] (3-D) array in [0,1] and --gt a [T,C,*spatial] array of per-frame velocities
+(elements per frame, channel 0 along W): gt(a, b) = velocity[a] * (b - a), exact for steady motion, every finite
+element valid, no occlusion split."""
+import argparse
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import ops
+from .evaluate import _pad32
+
+STATS = ("epe", "epe_noc", "epe_occ", "rmse", "ae_deg", "fl", "fl_noc", "fl_occ", "max_epe", "n_valid", "n_noc",
+         "n_nonfinite")
+DATASETS = {2: ("rectangle2d", "droplet2d"), 3: ("droplet3d", "jets3d")}
+
+
+def motion(name, frames, size, seed, device):
+    """(frames [T,*sp] on `device`, gt(t_from, t_to) -> (disp, valid, noc)) of a synthetic sequence."""
+    from .data import synthetic
+    if name == "rectangle2d":
+        f, gt = synthetic.rectangle2d_motion(frames, seed)
+        f = f.to(device)
+        return f, lambda a, b: tuple(t.to(device) for t in gt(a, b))
+    if name == "droplet2d":
+        h, w = (size + size)[:2] if size else (160, 224)
+        return synthetic.droplet2d_motion(frames, h, w, seed, device=device)
+    s = size[0] if size else 64
+    if name == "droplet3d":
+        return synthetic.droplet3d_motion(frames, s, seed, device=device)
+    if name == "jets3d":
+        return synthetic.jets3d_motion(frames, s, seed, device=device)
+    raise ValueError("unknown dataset %r" % name)
+
+
+def velocity_gt(vel):
+    """gt(a, b) of a [T,C,*sp] per-frame velocity array: vel[a] (b - a); valid where finite; noc = valid."""
+    def gt(a, b):
+        v = vel[a]
+        valid = torch.isfinite(v).all(0)
+        return torch.where(valid, v, torch.zeros_like(v)) * float(b - a), valid, valid.clone()
+    return gt
+
+
+def rife_pairs(T, gap):
+    if gap < 2 or gap % 2:
+        raise ValueError("the RIFE models score the mid frame of (t, t+g): g must be even, got %d" % gap)
+    return [(t, t + gap) for t in range(0, T - gap)]
+
+
+def _final_flow(model, a, b):
+    return model.inference(a, b)[1][-1]  # flow_list[2]: [B, 2C, *padded]
+
+
+def rife_flows(model, frames, pairs, batch):
+    """Final IFNet flows as displacements [2P, C, *sp]: (F_mid->0, F_mid->1) of every pair, inputs padded to multiples
+    of 32 as evaluate.interpolate_sequence does and the flows cropped back.  A Flow-3D flow is converted to a
+    displacement (ops.rife3d_to_disp, in fp64) BEFORE the crop: the model's warp sampled at ix = (h+F0)(Wp-1)/(Hp-1)
+    and so on with the PADDED extents, which differ from the cropped ones' ratios unless the volume is cubic."""
+    nd = frames.dim() - 1
+    sp = tuple(frames.shape[1:])
+    C = nd
+    x = _pad32(frames.to(torch.float32).unsqueeze(1), nd)
+    out = []
+    with torch.no_grad():
+        for i in range(0, len(pairs), batch):
+            chunk = pairs[i:i + batch]
+            a = x[torch.tensor([p[0] for p in chunk], device=x.device)]
+            b = x[torch.tensor([p[1] for p in chunk], device=x.device)]
+            f = _final_flow(model, a, b)
+            if nd == 3:
+                f = torch.cat([ops.rife3d_to_disp(f[:, :C].double()), ops.rife3d_to_disp(f[:, C:2 * C].double())],
+                              1).float()
+            f = f[(slice(None), slice(None)) + tuple(slice(0, s) for s in sp)]
+            out.append(torch.stack([f[:, :C], f[:, C:2 * C]], 1).reshape((-1, C) + sp))
+    return torch.cat(out, 0)
+
+
+def upflow_flows(net, frames, pairs, batch):
+    """(flow_f_out, flow_b_out) of every pair as [2P, 2, H, W]; grey frames replicated to 3 channels."""
+    out = []
+    with torch.no_grad():
+        for i in range(0, len(pairs), batch):
+            chunk = pairs[i:i + batch]
+            im1 = frames[[p[0] for p in chunk]].unsqueeze(1).repeat(1, 3, 1, 1).float()
+            im2 = frames[[p[1] for p in chunk]].unsqueeze(1).repeat(1, 3, 1, 1).float()
+            o = net({"im1": im1, "im2": im2, "if_loss": False})
+            out.append(torch.stack([o["flow_f_out"], o["flow_b_out"]], 1).reshape((-1, 2) + tuple(frames.shape[1:])))
+    return torch.cat(out, 0)
+
+
+def gt_stack(gt, targets):
+    """(disp [P,C,*sp], valid [P,*sp], noc [P,*sp]) of the (t_from, t_to) list `targets`."""
+    g = [gt(a, b) for a, b in targets]
+    return (torch.stack([x[0] for x in g]).float().contiguous(), torch.stack([x[1] for x in g]),
+            torch.stack([x[2] for x in g]))
+
+
+def _table(res, names):
+    rows = [{k: float(res[k][i]) for k in STATS} for i in range(len(names))]
+    mean = {k: float(np.nanmean([r[k] for r in rows])) if any(not np.isnan(r[k]) for r in rows) else float("nan")
+            for k in STATS}
+    return rows, mean
+
+
+def evaluate_flows(pred, targets, gt, convention, names, pairs, zero_baseline=False):
+    """Score `pred` [P,C,*sp] (under `convention`) against gt(t_from, t_to) for `targets` in one flow_metrics launch;
+    per pair and mean."""
+    disp, valid, noc = gt_stack(gt, targets)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = ops.flow_metrics(pred, disp, valid, noc, convention)
+    torch.cuda.synchronize()
+    t_metrics = time.perf_counter() - t0
+    rows, mean = _table(res, targets)
+    per_pair = []
+    k = len(names)
+    for i, (a, b) in enumerate(pairs):
+        entry = {"t0": a, "t1": b, "flows": {names[j]: dict(rows[k * i + j], t_from=targets[k * i + j][0],
+                                                             t_to=targets[k * i + j][1]) for j in range(k)}}
+        per_pair.append(entry)
+    doc = {"convention": convention, "pairs": per_pair, "mean": mean, "time_metrics_s": t_metrics}
+    if zero_baseline:
+        zr = ops.flow_metrics(torch.zeros_like(disp), disp, valid, noc, "disp")
+        zrows, zmean = _table(zr, targets)
+        doc["zero_baseline"] = {"mean": zmean, "flows": zrows}
+    return doc
+
+
+def _save(dirname, pred, targets):
+    os.makedirs(dirname, exist_ok=True)
+    p = pred.cpu().numpy()
+    for i, (a, b) in enumerate(targets):
+        np.save(os.path.join(dirname, "flow_%03d_to_%03d.npy" % (a, b)), p[i])
+
+
+def _common_args(nd, desc):
+    ap = argparse.ArgumentParser(description=desc)
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--dataset", choices=DATASETS[nd], help="synthetic sequence with known motion")
+    src.add_argument("--seq", help=".npy sequence [T,%s] in [0,1] (needs --gt)" % ",".join("DHW"[3 - nd:]))
+    ap.add_argument("--gt", help=".npy per-frame velocities [T,%d,%s] for --seq" % (nd, ",".join("DHW"[3 - nd:])))
+    ap.add_argument("--frames", type=int, default=9, help="frames of a synthetic sequence")
+    ap.add_argument("--size", type=int, nargs="+", default=None, help="synthetic extent (S, or H W in 2-D)")
+    ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--gap", type=int, default=2, help="score pairs (t, t+gap)")
+    ap.add_argument("--model", default="train_log", help="directory holding the weights")
+    ap.add_argument("--batch", type=int, default=1, help="pairs per model call")
+    ap.add_argument("--zero-baseline", action="store_true", help="also score a zero displacement")
+    ap.add_argument("--save-flows", default=None, metavar="DIR", help="write every predicted flow (as a displacement) as .npy here")
+    ap.add_argument("--out", default=None, help="write the results as JSON here")
+    return ap
+
+
+def _sequence(args, nd, dev):
+    if args.seq:
+        if not args.gt:
+            raise SystemExit("--seq needs --gt (per-frame velocities)")
+        frames = torch.from_numpy(np.load(args.seq).astype(np.float32)).to(dev)
+        vel = torch.from_numpy(np.load(args.gt).astype(np.float32)).to(dev)
+        if frames.dim() != nd + 1 or tuple(vel.shape) != (frames.shape[0], nd) + tuple(frames.shape[1:]):
+            raise ValueError("--seq must be [T,%s] and --gt [T,%d,%s], got %s and %s" % (
+                ",".join("DHW"[3 - nd:]), nd, ",".join("DHW"[3 - nd:]), tuple(frames.shape), tuple(vel.shape)))
+        return frames, velocity_gt(vel), os.path.basename(args.seq)
+    frames, gt = motion(args.dataset, args.frames, args.size, args.seed, dev)
+    return frames, gt, args.dataset
+
+
+def _finish(doc, args, frames, name, t_inf):
+    doc.update(sequence=name, shape=list(frames.shape), gap=args.gap, batch=args.batch, time_inference_s=t_inf)
+    m = doc["mean"]
+    line = "%s gap %d: EPE %.4f (noc %.4f, occ %.4f)  Fl %.4f  AE %.3f deg  RMSE %.4f" % (
+        name, args.gap, m["epe"], m["epe_noc"], m["epe_occ"], m["fl"], m["ae_deg"], m["rmse"])
+    if "zero_baseline" in doc:
+        line += "  | zero flow EPE %.4f" % doc["zero_baseline"]["mean"]["epe"]
+    print(line + "  | inference %.3f s  metrics %.4f s" % (t_inf, doc["time_metrics_s"]))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+    return doc
+
+
+def main_rife(Model, nd, argv=None):
+    """flow2d / flow3d: the final IFNet flow at the mid frame of (t, t+gap)."""
+    args = _common_args(nd, "score the flows of a RIFE model against known motion").parse_args(argv)
+    dev = torch.device("cuda")
+    model = Model(-1, device=dev)
+    try:
+        model.load_model("flownet.pkl", args.model)
+    except FileNotFoundError:
+        print("no flownet.pkl under %s: using random-init weights" % args.model)
+    model.eval()
+    frames, gt, name = _sequence(args, nd, dev)
+    pairs = rife_pairs(frames.shape[0], args.gap)
+    targets = []
+    for a, b in pairs:
+        mid = (a + b) // 2
+        targets += [(mid, a), (mid, b)]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pred = rife_flows(model, frames, pairs, args.batch)
+    torch.cuda.synchronize()
+    t_inf = time.perf_counter() - t0
+    doc = evaluate_flows(pred, targets, gt, "disp", ["mid->t0", "mid->t1"], pairs, args.zero_baseline)
+    doc["model"] = args.model
+    doc["model_flow"] = "rife3d, converted at the padded extents" if nd == 3 else "disp"
+    if args.save_flows:
+        _save(args.save_flows, pred, targets)
+    return _finish(doc, args, frames, name, t_inf)
+
+
+def main_upflow(make_net, argv=None):
+    """upflow: flow_f_out of (t, t+gap) and flow_b_out of (t+gap, t)."""
+    ap = _common_args(2, "score UPFlow's forward and backward flows against known motion")
+    ap.set_defaults(gap=1)
+    args = ap.parse_args(argv)
+    if args.gap < 1:
+        raise SystemExit("--gap must be >= 1")
+    net = make_net(args.model)
+    dev = torch.device("cuda")
+    frames, gt, name = _sequence(args, 2, dev)
+    pairs = [(t, t + args.gap) for t in range(0, frames.shape[0] - args.gap)]
+    targets = []
+    for a, b in pairs:
+        targets += [(a, b), (b, a)]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pred = upflow_flows(net, frames, pairs, args.batch)
+    torch.cuda.synchronize()
+    t_inf = time.perf_counter() - t0
+    doc = evaluate_flows(pred, targets, gt, "disp", ["t0->t1", "t1->t0"], pairs, args.zero_baseline)
+    doc["model"] = args.model
+    if args.save_flows:
+        _save(args.save_flows, pred, targets)
+    return _finish(doc, args, frames, name, t_inf)

@@ -2295,3 +2295,195 @@ def frame_metrics(pred, gt, data_range=1.0, window="2d"):
     mse = sums[0] / per
     psnr = 10.0 * torch.log10((L * L) / mse)  # mse == 0 -> L^2/0 = inf -> +inf
     return psnr, sums[1] / valid
+
+
+# --------------------------------------------------------------------------------------------
+# Flow accuracy: EPE / RMSE / angular error / KITTI Fl against a ground-truth displacement (fs_flow_metrics{2,3}d)
+# --------------------------------------------------------------------------------------------
+FLOW_DISP, FLOW_RIFE3D = 0, 1
+_FLOW_CONVENTIONS = {"disp": FLOW_DISP, "rife3d": FLOW_RIFE3D}
+FLOW_METRICS_K = 13  # FS_FLOW_METRICS_K: the per-flow sums, in the order include/flowsci_hip.h documents
+
+
+def flow_metrics_cost(shape, masks=2, write_map=False):
+    """(HBM bytes, flops) the algorithm needs for one flow_metrics call on [N,C,*spatial] flows: both flows read once,
+    `masks` uint8 masks read once, the fp32 EPE map written once if asked; ~60 flops per element (differences, norms,
+    the cross product, the atan2 and the sums)."""
+    n = 1
+    for s in shape:
+        n *= int(s)
+    elems = n // int(shape[1])
+    return 2 * 4 * n + masks * elems + (4 * elems if write_map else 0), 60 * elems
+
+
+def rife3d_to_disp(flow):
+    """Displacement (x along W, y along H, z along D) of a Flow-3D flow [N,3,D,H,W]: the model's warp samples the input
+    at ix = (h+F0)(W-1)/(H-1), iy = (d+F1)(H-1)/(D-1), iz = (w+F2)(D-1)/(W-1) (Flow-3D/model/warplayer.py, the axis
+    rotation), so x = ix - w, y = iy - h, z = iz - d -- not clamped.  A flow of zero is not "no motion".  Plain torch
+    element-wise ops in the flow's dtype (not a hot path); every extent must be >= 2."""
+    D, H, W = _rife3d_extent(flow)
+    d, h, w = _dhw(flow)
+    return torch.stack([(h + flow[:, 0]) * ((W - 1) / (H - 1)) - w,
+                        (d + flow[:, 1]) * ((H - 1) / (D - 1)) - h,
+                        (w + flow[:, 2]) * ((D - 1) / (W - 1)) - d], 1)
+
+
+def disp_to_rife3d(disp):
+    """Inverse of rife3d_to_disp: the Flow-3D flow [N,3,D,H,W] whose warp samples the input at (w + x, h + y, d + z),
+    i.e. the flow that lets a ground-truth displacement drive the model's own warp (ops.warp3d)."""
+    D, H, W = _rife3d_extent(disp)
+    d, h, w = _dhw(disp)
+    return torch.stack([(w + disp[:, 0]) * ((H - 1) / (W - 1)) - h,
+                        (h + disp[:, 1]) * ((D - 1) / (H - 1)) - d,
+                        (d + disp[:, 2]) * ((W - 1) / (D - 1)) - w], 1)
+
+
+def _rife3d_extent(t):
+    if not isinstance(t, torch.Tensor) or t.dim() != 5 or t.shape[1] != 3:
+        raise ValueError("a 3-D flow must be [N,3,D,H,W], got %s" % (tuple(t.shape) if isinstance(t, torch.Tensor)
+                                                                      else type(t).__name__,))
+    D, H, W = (int(s) for s in t.shape[2:])
+    if min(D, H, W) < 2:
+        raise ValueError("the rife3d convention needs every extent >= 2, got %s" % (tuple(t.shape),))
+    return D, H, W
+
+
+def _dhw(t):
+    D, H, W = t.shape[2:]
+    kw = dict(dtype=t.dtype, device=t.device)
+    return (torch.arange(D, **kw).view(1, D, 1, 1), torch.arange(H, **kw).view(1, 1, H, 1),
+            torch.arange(W, **kw).view(1, 1, 1, W))
+
+
+def _flow_operand(name, t, nd):
+    """[N,C,*sp] fp32 on a GPU whose C planes per flow are contiguous [C,*sp] blocks: the batch stride may be anything
+    (a channel slice flow[:, C:2C] passes as it is).  Anything else is converted / copied once."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s must be a tensor" % name)
+    if not t.is_cuda:
+        raise ValueError("%s must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (name, t.device))
+    if t.dim() != nd + 2 or t.shape[1] != nd:
+        raise ValueError("%s must be [N,%d,%s], got shape %s" % (name, nd, ",".join("DHW"[3 - nd:]), tuple(t.shape)))
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    inner = t[0] if t.shape[0] > 0 else t
+    if t.shape[0] > 0 and not inner.is_contiguous():
+        t = t.contiguous()
+    if t.shape[0] > 1 and t.stride(0) < inner.numel():
+        t = t.contiguous()
+    return t
+
+
+def _flow_mask(name, m, shape, device):
+    if m is None:
+        return None
+    if not isinstance(m, torch.Tensor):
+        raise ValueError("%s must be a tensor or None" % name)
+    if m.device != device:
+        raise ValueError("%s must be on the flows' device %s, got %s" % (name, device, m.device))
+    if m.dim() == len(shape) + 1 and m.shape[1] == 1:
+        m = m[:, 0]
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError("%s must be [N,*spatial] = %s, got %s" % (name, tuple(shape), tuple(m.shape)))
+    if m.dtype == torch.bool:
+        m = m.contiguous().view(torch.uint8)
+    elif m.dtype == torch.uint8:
+        m = m.contiguous()
+    else:
+        m = (m != 0).contiguous().view(torch.uint8)
+    return m
+
+
+def flow_metrics(pred, gt, valid=None, noc=None, convention="disp", tau=(3.0, 0.05), return_map=False):
+    """Accuracy of N predicted flows against N ground-truth displacements, one launch (fs_flow_metrics{2,3}d).
+
+    pred, gt: [N,2,H,W] (channel 0 along W, 1 along H) or [N,3,D,H,W] (0 along W, 1 along H, 2 along D), in elements,
+    on a GPU.  A channel slice such as IFNet's flow[:, C:2C] is read in place (only the per-flow [C,*sp] block has to
+    be contiguous).  valid / noc: optional bool or uint8 [N,*sp] masks; valid None = all valid, noc None = no
+    occlusion split (the noc / occ entries are NaN); noc counts only where valid is set.
+    convention: "disp" (pred is a displacement: 2-D RIFE and PWC / UPFlow flows) or "rife3d" (a Flow-3D flow, whose
+    warp rotates axes: converted to a displacement inside the kernel, as rife3d_to_disp does; every extent >= 2).
+    gt is always a displacement.  tau = (tau_abs, tau_rel): an element is an outlier (KITTI Fl) when
+    epe > tau_abs and epe > tau_rel |gt|.
+
+    Returns a dict of fp64 [N] tensors: epe, epe_noc, epe_occ (mean end-point error over valid / noc / valid minus noc),
+    rmse, ae_deg (Barron's angular error between (p, 1) and (g, 1), degrees), fl, fl_noc, fl_occ (outlier fractions),
+    max_epe, n_valid, n_noc, n_nonfinite; with return_map=True also epe_map, fp32 [N,*sp] (epe at every element,
+    NaN where pred or gt is not finite).  An element whose pred or gt is not finite counts as an outlier and in
+    n_nonfinite, and is left out of the means and the max.  An empty subset gives NaN."""
+    if convention not in _FLOW_CONVENTIONS:
+        raise ValueError("convention must be 'disp' or 'rife3d', got %r" % (convention,))
+    if not isinstance(pred, torch.Tensor) or pred.dim() not in (4, 5):
+        raise ValueError("pred must be [N,2,H,W] or [N,3,D,H,W], got %s" %
+                         (tuple(pred.shape) if isinstance(pred, torch.Tensor) else type(pred).__name__,))
+    nd = pred.dim() - 2
+    pred = _flow_operand("pred", pred, nd)
+    gt = _flow_operand("gt", gt, nd)
+    if pred.shape != gt.shape:
+        raise ValueError("pred and gt differ in shape: %s vs %s" % (tuple(pred.shape), tuple(gt.shape)))
+    if pred.device != gt.device:
+        raise ValueError("pred and gt are on different devices")
+    conv = _FLOW_CONVENTIONS[convention]
+    if conv == FLOW_RIFE3D and nd != 3:
+        raise ValueError("convention 'rife3d' is for [N,3,D,H,W] Flow-3D flows")
+    sp = tuple(int(s) for s in pred.shape[2:])
+    if conv == FLOW_RIFE3D and min(sp) < 2:
+        raise ValueError("the rife3d convention needs every extent >= 2, got %s" % (tuple(pred.shape),))
+    tau_abs, tau_rel = (float(v) for v in tau)
+    if not (0 <= tau_abs < float("inf") and 0 <= tau_rel < float("inf")):
+        raise ValueError("tau must be two finite values >= 0, got %r" % (tau,))
+    N = int(pred.shape[0])
+    mshape = (N,) + sp
+    valid = _flow_mask("valid", valid, mshape, pred.device)
+    noc_m = _flow_mask("noc", noc, mshape, pred.device)
+    emap = torch.empty(mshape, dtype=torch.float32, device=pred.device) if return_map else None
+    if N == 0:
+        res = {k: torch.empty(0, dtype=torch.float64, device=pred.device) for k in _FLOW_KEYS}
+        if return_map:
+            res["epe_map"] = emap
+        return res
+    lib = _lib.lib()
+    nb = (lib.fs_flow_metrics2d_ws_bytes(N, nd, *sp) if nd == 2 else
+          lib.fs_flow_metrics3d_ws_bytes(N, nd, *sp, conv))
+    if nb < 0:
+        _lib.check(int(-nb), "fs_flow_metrics%dd_ws_bytes" % nd)
+    ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=pred.device)
+    out = torch.empty(N, FLOW_METRICS_K, dtype=torch.float64, device=pred.device)
+    nbytes, flops = flow_metrics_cost(pred.shape, (valid is not None) + (noc_m is not None), return_map)
+    P = 1
+    for v in sp:
+        P *= v
+    pbs = pred.stride(0) if N > 1 else nd * P  # (a single flow's batch stride is never used)
+    gbs = gt.stride(0) if N > 1 else nd * P
+    args = (pred.data_ptr(), gt.data_ptr(), N, nd) + sp + (pbs, gbs, _ptr(valid), _ptr(noc_m))
+    args += ((conv,) if nd == 3 else ()) + (tau_abs, tau_rel, _ptr(emap), ws.data_ptr(), out.data_ptr(), _stream(pred))
+    with torch.cuda.device(pred.device):
+        _call("fs_flow_metrics%dd" % nd, *args, algo_bytes=nbytes, algo_flops=flops)
+    return _flow_stats(out, noc is not None, emap)
+
+
+_FLOW_KEYS = ("epe", "epe_noc", "epe_occ", "rmse", "ae_deg", "fl", "fl_noc", "fl_occ", "max_epe", "n_valid", "n_noc",
+              "n_nonfinite")
+
+
+def _flow_stats(out, split, emap):
+    """The per-flow statistics from the kernel's sums `out` [N, K] (fp64)."""
+    nan = torch.tensor(float("nan"), dtype=torch.float64, device=out.device)
+
+    def div(a, b):
+        return torch.where(b > 0, a / torch.where(b > 0, b, torch.ones_like(b)), nan)
+
+    n, s1, s2, sae, nout, mx = (out[:, k] for k in range(6))
+    nn, s1n, s2n, saen, noutn = (out[:, k] for k in range(6, 11))
+    nf, nfn = out[:, 11], out[:, 12]
+    fin, finn = n - nf, nn - nfn
+    res = {"epe": div(s1, fin), "rmse": torch.sqrt(div(s2, fin)), "ae_deg": torch.rad2deg(div(sae, fin)),
+           "fl": div(nout, n), "max_epe": torch.where(fin > 0, mx, nan), "n_valid": n, "n_nonfinite": nf}
+    if split:
+        res.update(epe_noc=div(s1n, finn), epe_occ=div(s1 - s1n, fin - finn), fl_noc=div(noutn, nn),
+                   fl_occ=div(nout - noutn, n - nn), n_noc=nn)
+    else:
+        res.update({k: torch.full_like(n, float("nan")) for k in ("epe_noc", "epe_occ", "fl_noc", "fl_occ", "n_noc")})
+    if emap is not None:
+        res["epe_map"] = emap
+    return res
