@@ -6,6 +6,7 @@ stream of the operand's device.  Nothing here computes on the CPU: without a GPU
 libflowsci_hip.so these functions raise.
 """
 import ctypes
+from fractions import Fraction
 
 import torch
 
@@ -77,34 +78,18 @@ def kernel_timings():
     return {k: [(a.elapsed_time(b), nb, fl, fe, sym) for a, b, nb, fl, fe, sym in v] for k, v in _timing.items()}
 
 
-def _call(name, *args, algo_bytes=0, algo_flops=0, record_as=None, equiv_flops=None, kernel=None):
-    """Launch a C-ABI entry point.  `algo_bytes` / `algo_flops` = compulsory HBM bytes / useful flops of
-    this launch, only used by the optional timing records (`record_as`: file the record
-    under another entry point's name -- the *_prelu variants are the same kernels with one more store)."""
+def _call(name, *args, algo_bytes=0, algo_flops=0, record_as=None, equiv_flops=None, kernel=None, allow=()):
+    """Launch a C-ABI entry point and return its status: 0, or one in `allow` (FS_ERR_UNSUPPORTED: "no such kernel
+    for this shape, take the unfused path"); any other status raises.  `algo_bytes` / `algo_flops` = compulsory HBM
+    bytes / useful flops of this launch, only used by the optional timing records (`record_as`: file
+    the record under another entry point's name -- the *_prelu variants are the same kernels with one more store)."""
     fn = getattr(_lib.lib(), name)
     if _timing is None or (_timing_only is not None and (record_as or name) not in _timing_only):
-        _lib.check(fn(*args), name)
-        return
-    e0 = torch.cuda.Event(enable_timing=True)
-    e1 = torch.cuda.Event(enable_timing=True)
-    e0.record()
-    code = fn(*args)
-    e1.record()
-    _lib.check(code, name)
-    _timing.setdefault(record_as or name, []).append((e0, e1, algo_bytes, algo_flops,
-                                                      algo_flops if equiv_flops is None else equiv_flops, kernel))
-
-
-def _call_rc(name, *args, algo_bytes=0, algo_flops=0, record_as=None, allow=(), equiv_flops=None, kernel=None):
-    """_call for entry points that may answer with a status in `allow` (FS_ERR_UNSUPPORTED: "no such kernel for
-    this shape, take the unfused path"): returns the status instead of raising on those."""
-    fn = getattr(_lib.lib(), name)
-    timed = not (_timing is None or (_timing_only is not None and (record_as or name) not in _timing_only))
-    if timed:
+        rc = fn(*args)
+    else:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    rc = fn(*args)
-    if timed:
+        rc = fn(*args)
         e1.record()
         if rc == 0:
             _timing.setdefault(record_as or name, []).append((e0, e1, algo_bytes, algo_flops,
@@ -112,6 +97,71 @@ def _call_rc(name, *args, algo_bytes=0, algo_flops=0, record_as=None, allow=(), 
     if rc not in allow:
         _lib.check(rc, name)
     return rc
+
+
+# The kernel a convolution or 3-D warp launch runs, by the library's own plan for its geometry: the slab kind of
+# fs_conv3d_{fwd,tr}_wprep_jobs (FS_WPREP_* in csrc/wprep.hpp), the id of fs_conv3d_wrw_kernel_id (FS_WRW_KERNEL_*) or
+# of fs_warp3d_kernel_id (FS_W3_KERNEL_*, both in include/flowsci_hip.h) -> (its symbol as `rocprofv3 --kernel-trace
+# --stats` prints it, matrix-core flops EXECUTED per flop of the direct formulation).  Either may be a function of
+# (C, W): the launch's output channels and output width (wrw: the gradient's).  The split-bf16 kernels execute six bf16
+# products per fp32 multiply-add (priced against the bf16 peak), the Winograd forms 2/3, 1/2 or 1/3 of the direct
+# form's multiply-adds.  A plan not listed runs one of several fp32 instantiations: no symbol, the direct flops.
+_KERNELS = {
+    ("fwd", 4): (None, Fraction(2, 3)),  # FS_WPREP_WINO: F(2,3) along x (ablation build)
+    ("fwd", 5): (None, Fraction(1, 2)),  # FS_WPREP_WINO4: F(4,3) along x (ablation build)
+    ("fwd", 6): (lambda C, W: "conv3d_wino2d_ps_kernel<0, %d>" % (16 if W % 64 == 0 else 8),  # FS_WPREP_WINO2D
+                 Fraction(1, 3)),
+    ("fwd", 7): (lambda C, W: "conv3d_fwd_s3_kernel<%d, 8, 4>" % (1 if C <= 32 else 2), 6),  # FS_WPREP_S3K4
+    ("tr", 8): ("convtr_s3_kernel<false>", lambda C, W: Fraction(6 * 32 * ((C + 31) // 32), C)),  # FS_WPREP_TRS3
+    ("tr", 9): ("convtr_s3_kernel<true>", lambda C, W: Fraction(6 * 16, C)),  # FS_WPREP_TRS3_16
+    ("wrw", 2): (None, Fraction(2, 3)),  # FS_WRW_KERNEL_WINO23 (ablation build)
+    ("wrw", 3): ("conv3d_wrw_wino4_kernel<0>", Fraction(1, 2)),  # FS_WRW_KERNEL_WINO43
+    ("wrw", 4): (lambda C, W: "conv3d_wrw_s3_kernel<8, 2, 1, 2, 4, 0, %d>" % (16 if W == 16 else 32) if C > 32
+                 else "conv3d_wrw_s3_kernel<6, 1, 2, 2, 3, 0, 32>", 6),  # FS_WRW_KERNEL_S3
+    ("warp3d_fwd", 1): ("warp3d_rc_kernel<false, 2, 6, 0>", 0),  # FS_W3_KERNEL_RC
+    ("warp3d_bwd", 1): ("warp3d_rc_kernel<true, 4, 5, 0>", 0),
+}
+_plans = {}  # (family, misalignments) + geometry -> (plan id, (kernel symbol, flops executed, direct flops))
+
+
+def _plan(family, mis, geo):
+    """The library's plan for one launch of `family` ('fwd', 'tr', 'wrw', 'warp3d_fwd', 'warp3d_bwd'), asked once per
+    key and nothing launched: (plan id, (kernel symbol or None, matrix-core flops executed, flops of the direct
+    formulation)).  `geo`: the shape arguments of the family's query in its order; `mis`: the 16-byte misalignment of
+    each pointer that query inspects (it is handed placeholders)."""
+    key = (family, mis) + geo
+    hit = _plans.get(key)
+    if hit is not None:
+        return hit
+    L = _lib.lib()
+    ptrs = [0x1000 + m for m in mis]
+    if family in ("fwd", "tr"):  # B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, then k, stride, pad, wmode (fwd) / has_z (tr)
+        B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo = geo[:9]
+        jobs = (_lib.FsWprepJob * 8)()
+        query = L.fs_conv3d_fwd_wprep_jobs if family == "fwd" else L.fs_conv3d_tr_wprep_jobs
+        n = query(jobs, 8, *ptrs, 0x1000, 0x1000, *geo)
+        kinds = {jobs[i].kind for i in range(min(n, 8))}
+        pid = kinds.pop() if len(kinds) == 1 else None
+        C, W = Cout, Wo
+        direct = 2 * B * Cin * Cout * (geo[9] ** 3 * Do * Ho * Wo if family == "fwd" else 64 * Di * Hi * Wi)
+    elif family == "wrw":  # B, Cg, Cs, Do, Ho, Wo, Di, Hi, Wi, k, stride, pad
+        B, C, Cs, Do, Ho, W = geo[:6]
+        pid = int(L.fs_conv3d_wrw_kernel_id(*ptrs, *geo))
+        direct = 2 * B * C * Cs * geo[9] ** 3 * Do * Ho * W
+    else:  # B, C, Di, Hi, Wi, D, H, W, with_grad_in
+        B, C, Di, Hi, Wi, D, H, W, with_grad_in = geo
+        pid = int(L.fs_warp3d_kernel_id(*ptrs, B, C, (ctypes.c_int * 3)(Di, Hi, Wi), D, H, W,
+                                        int(family == "warp3d_bwd"), with_grad_in))
+        direct = 0
+    sym, factor = (v(C, W) if callable(v) else v for v in _KERNELS.get((family, pid), (None, 1)))
+    hit = _plans[key] = (pid, (sym, int(direct * factor), direct))
+    return hit
+
+
+def _kernel_accounting(family, mis, *geo):
+    """(kernel symbol or None, matrix-core flops executed, flops of the direct formulation) of a launch, for the timing
+    records (see _plan); (None, 0, 0) without asking anything while launches are not timed."""
+    return (None, 0, 0) if _timing is None else _plan(family, mis, geo)[1]
 
 
 # --------------------------------------------------------------------------------------------
@@ -295,22 +345,6 @@ def _check_pair(img0, img1, flow):
     return img0, img1, flow, nd
 
 
-_W3_SYMBOLS = {(0, 1): "warp3d_rc_kernel<false, 2, 6, 0>", (1, 1): "warp3d_rc_kernel<true, 4, 5, 0>"}
-
-
-def _warp3d_symbol(img0, img1, flow, backward, with_grad_in=False):
-    """Kernel symbol a trilinear-warp pair launch of this geometry dispatches to, where ops.py can name it for bench.py's
-    per-symbol records: the round-5 row-cache ring kernels (fs_warp3d_kernel_id; asked only while launches are being
-    timed).  None = the gather kernels (several instantiations)."""
-    if _timing is None:
-        return None
-    B, C = img0.shape[:2]
-    D, H, W = flow.shape[2:]
-    kid = int(_lib.lib().fs_warp3d_kernel_id(img0.data_ptr(), img1.data_ptr(), flow.data_ptr(), B, C, _in_dhw(img0, flow),
-                                             D, H, W, int(backward), int(with_grad_in)))
-    return _W3_SYMBOLS.get((int(backward), kid))
-
-
 def _pair_forward(img0, img1, flow, nd):
     oshape = tuple(img0.shape[:2]) + tuple(flow.shape[2:])  # the warps take the flow's extent
     out0, out1 = img0.new_empty(oshape), img1.new_empty(oshape)
@@ -318,10 +352,12 @@ def _pair_forward(img0, img1, flow, nd):
     with torch.cuda.device(flow.device):
         if nd == 3:
             D, H, W = flow.shape[2:]
+            mis = (img0.data_ptr() % 16, img1.data_ptr() % 16, flow.data_ptr() % 16)
+            sym, fl, fq = _kernel_accounting("warp3d_fwd", mis, B, C, *img0.shape[2:], D, H, W, 0)
             _call("fs_warp3d_pair_fwd", img0.data_ptr(), img1.data_ptr(), flow.data_ptr(),
                   out0.data_ptr(), out1.data_ptr(), B, C, _in_dhw(img0, flow), D, H, W,
-                  _stream(flow), algo_bytes=4 * flow.numel() + 8 * out0.numel() * 2,
-                  kernel=_warp3d_symbol(img0, img1, flow, 0))
+                  _stream(flow), algo_bytes=4 * flow.numel() + 8 * out0.numel() * 2, algo_flops=fl, equiv_flops=fq,
+                  kernel=sym)
         else:
             H, W = flow.shape[2:]
             _call("fs_warp2d_pair_fwd", img0.data_ptr(), img1.data_ptr(), flow.data_ptr(),
@@ -391,21 +427,23 @@ def _pair_backward(img0, img1, flow, g0, g1, need_img, need_flow, gflow_add=None
         if flow.dim() == 5:
             D, H, W = flow.shape[2:]
             nb = 8 * flow.numel() + 8 * g0.numel() * 2 + (8 * img0.numel() if need_img else 0)
+            mis = (img0.data_ptr() % 16, img1.data_ptr() % 16, flow.data_ptr() % 16)
+            sym, fl, fq = _kernel_accounting("warp3d_bwd", mis, B, C, *img0.shape[2:], D, H, W, int(need_img))
             if gflow_add is not None:
                 adds = gflow_add if isinstance(gflow_add, (list, tuple)) else [gflow_add]
                 aargs, keep, abytes = _flow_addends(adds, flow)
                 gflow = torch.empty_like(flow)
                 _call("fs_warp3d_pair_bwd_acc3", img0.data_ptr(), img1.data_ptr(), flow.data_ptr(),
                       g0.data_ptr(), s0, g1.data_ptr(), s1, _ptr(gi0), _ptr(gi1), *aargs, gflow.data_ptr(),
-                      B, C, _in_dhw(img0, flow), D, H, W, _stream(flow), algo_bytes=nb + abytes,
-                      kernel=_warp3d_symbol(img0, img1, flow, 1, need_img))
+                      B, C, _in_dhw(img0, flow), D, H, W, _stream(flow), algo_bytes=nb + abytes, algo_flops=fl,
+                      equiv_flops=fq, kernel=sym)
                 del keep
             else:
                 gflow = torch.empty_like(flow) if need_flow else None
                 _call("fs_warp3d_pair_bwd", img0.data_ptr(), img1.data_ptr(), flow.data_ptr(),
                       g0.data_ptr(), g1.data_ptr(), _ptr(gi0), _ptr(gi1), _ptr(gflow), B, C,
-                      _in_dhw(img0, flow), D, H, W, _stream(flow), algo_bytes=nb,
-                      kernel=_warp3d_symbol(img0, img1, flow, 1, need_img))
+                      _in_dhw(img0, flow), D, H, W, _stream(flow), algo_bytes=nb, algo_flops=fl, equiv_flops=fq,
+                      kernel=sym)
         else:
             H, W = flow.shape[2:]
             gflow = torch.empty_like(flow) if need_flow else None
@@ -1656,68 +1694,12 @@ def _prep_not_written():
         _last_prep.stamp = None
 
 
-_wino_seen = {}
-
-
-def _fwd_k3_macs(xptr, B, Cin, Cout, dhw, wmode):
-    """Multiply-adds per output and input channel that fs_conv3d_fwd* EXECUTES for this k3 s1 p1 call: 27 as a direct
-    implicit GEMM, 18 as the 1-D Winograd F(2,3) kernel (csrc/convwino.hpp), 13.5 as F(4,3) (csrc/convwino4.hpp), 9 as the
-    2-D F(2,3) x F(4,3) kernel (csrc/convwino2d.hpp).
-    Asked of the library's own dispatch (its re-layout plan), cached per geometry; only the flop accounting of the
-    timing records depends on it."""
-    key = (xptr % 16, B, Cin, Cout) + tuple(int(v) for v in dhw) + (int(wmode),)
-    if key not in _wino_seen:
-        buf = (_lib.FsWprepJob * 4)()
-        n = _lib.lib().fs_conv3d_fwd_wprep_jobs(buf, 4, 0x1000 + xptr % 16, 0x1000, 0x1000, B, Cin, Cout, *key[4:7],
-                                                *key[4:7], 3, 1, 1, int(wmode))
-        _wino_seen[key] = {4: 18.0, 5: 13.5, 6: 9.0}.get(buf[0].kind, 27.0) if n == 1 else 27.0
-    return _wino_seen[key]
-
-
-def _fwd_k4_symbol(xptr, B, Cin, Cout, in_dhw, out_dhw):
-    """Kernel symbol of a k4 s2 p1 fs_conv3d_fwd* call where ops.py can name it: the round-5 kernel that runs the layer
-    with fp32 accuracy on the bf16 matrix rate (csrc/convfwd_s3.hpp; the library's re-layout plan says slab kind 7).  Asked
-    only while launches are being timed; None = the fp32-MFMA kernels (several instantiations)."""
-    if _timing is None:
-        return None
-    key = ("k4", xptr % 16, B, Cin, Cout) + tuple(int(v) for v in in_dhw)
-    if key not in _wino_seen:
-        buf = (_lib.FsWprepJob * 4)()
-        n = _lib.lib().fs_conv3d_fwd_wprep_jobs(buf, 4, 0x1000 + xptr % 16, 0x1000, 0x1000, B, Cin, Cout, *key[5:8],
-                                                *[int(v) for v in out_dhw], 4, 2, 1, 0)
-        _wino_seen[key] = (n == 1 and buf[0].kind == 7)
-    return ("conv3d_fwd_s3_kernel<%d, 8, 4>" % (1 if Cout <= 32 else 2)) if _wino_seen[key] else None
-
-
-def _tr_symbol(xptr, B, Cin, Cout, in_dhw, out_dhw, has_z):
-    """Kernel symbol of an fs_conv3d_tr* call where ops.py can name it: the round-5 split-bf16 kernels (csrc/convtr_s3.hpp;
-    the library's re-layout plan says slab kind 8 = the 32-row form, 9 = the 16-row form).  Asked only while launches are
-    being timed; None = the fp32-MFMA kernels."""
-    if _timing is None:
-        return None
-    key = ("tr", xptr % 16, B, Cin, Cout, int(has_z)) + tuple(int(v) for v in in_dhw) + tuple(int(v) for v in out_dhw)
-    if key not in _wino_seen:
-        buf = (_lib.FsWprepJob * 8)()
-        n = _lib.lib().fs_conv3d_tr_wprep_jobs(buf, 8, 0x1000 + xptr % 16, 0x1000, 0x1000, B, Cin, Cout, *key[6:12], int(has_z))
-        kinds = set(buf[i].kind for i in range(max(n, 0)))
-        _wino_seen[key] = "convtr_s3_kernel<false>" if kinds == {8} else ("convtr_s3_kernel<true>" if kinds == {9} else None)
-    return _wino_seen[key]
-
-
-def _fwd_k3_symbol(macs, W):
-    """Kernel symbol of a k3 s1 p1 fs_conv3d_fwd* call whose dispatch executes `macs` multiply-adds per (output, input
-    channel) -- the names `rocprofv3 --kernel-trace --stats` prints (csrc/convwino2d.hpp::launch_wino2d: 16 x-tiles per
-    row on rows of 64 voxels, 8 on rows of 32); None for the direct kernels (several instantiations by shape)."""
-    return "conv3d_wino2d_ps_kernel<0, %d>" % (16 if int(W) % 64 == 0 else 8) if macs == 9.0 else None
-
-
-def _prepared_fwd(w, xptr, B, Cin, Cout, in_dhw, out_dhw, k, stride, pad, wmode):
-    """Slab of fs_conv3d_fwd* for this call: which layout (direct taps, or the Winograd-transformed filter of the
-    64-channel k3 trunk layers) is the library's decision for the call's geometry."""
+def _prepared_fwd(w, xptr, geo):
+    """Slab of fs_conv3d_fwd* for a call of geometry `geo` (B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, k, stride, pad,
+    wmode): which layout (direct taps, or the Winograd-transformed filter of the 64-channel k3 trunk layers) is the
+    library's decision for the call's geometry."""
     L = _lib.lib()
-    geo = (B, Cin, Cout) + tuple(int(v) for v in in_dhw) + tuple(int(v) for v in out_dhw) + (int(k), int(stride), int(pad),
-                                                                                          int(wmode))
-    return _prepared(w, L.fs_conv3d_fwd_ws_floats(Cin, Cout, int(k)), ("fwd", xptr % 16) + geo,
+    return _prepared(w, L.fs_conv3d_fwd_ws_floats(geo[1], geo[2], geo[9]), ("fwd", xptr % 16) + geo,
                      lambda jobs, cap, ws: L.fs_conv3d_fwd_wprep_jobs(jobs, cap, xptr, w.data_ptr(), ws.data_ptr(), *geo))
 
 
@@ -1776,10 +1758,10 @@ def _dw_zeros(like, shape):
     return out
 
 
-def _conv3d_wrw_det(g, src_ptr, pv, sv, geo, nbytes, flops, equiv, allow_unsupported=False, kernel=None):
+def _conv3d_wrw_det(g, src_ptr, pv, sv, geo, nbytes, acct, allow_unsupported=False):
     """fs_conv3d_wrw_det: the same kernels with every run of positions storing its partial tile into its own copy of dW
     (a workspace of runs x |dW| floats) and one more launch adding the copies in run order -- no float atomics, bitwise
-    reproducible.  Taken when torch.are_deterministic_algorithms_enabled()."""
+    reproducible.  Taken when torch.are_deterministic_algorithms_enabled().  `acct`: the call's _kernel_accounting."""
     L = _lib.lib()
     need = int(L.fs_conv3d_wrw_det_ws_floats(g.data_ptr(), src_ptr, pv, sv, *geo))
     if need == -FS_ERR_UNSUPPORTED and allow_unsupported:
@@ -1790,9 +1772,10 @@ def _conv3d_wrw_det(g, src_ptr, pv, sv, geo, nbytes, flops, equiv, allow_unsuppo
     k = geo[9]
     dw = g.new_empty(Cg, Cs, k, k, k)
     ws = g.new_empty(max(need, 1))
+    sym, fl, fq = acct
     with torch.cuda.device(g.device):
         _call("fs_conv3d_wrw_det", g.data_ptr(), src_ptr, pv, sv, dw.data_ptr(), ws.data_ptr(), need, *geo, _stream(g),
-              algo_bytes=nbytes, algo_flops=flops, equiv_flops=equiv, record_as="fs_conv3d_wrw", kernel=kernel)
+              algo_bytes=nbytes, algo_flops=fl, equiv_flops=fq, record_as="fs_conv3d_wrw", kernel=sym)
     return dw
 
 
@@ -1804,31 +1787,16 @@ def conv3d_wrw(g, src, k, stride, pad):
     Cs = src.shape[1]
     if src.shape[0] != B:
         raise ValueError("batch mismatch")
-    fq = 2 * g.numel() * Cs * int(k) ** 3
-    kid = conv3d_wrw_kernel_id(g.data_ptr(), src.data_ptr(), B, Cg, Cs, g.shape[2:], src.shape[2:], k, stride, pad)
     geo = (B, Cg, Cs, g.shape[2], g.shape[3], g.shape[4], src.shape[2], src.shape[3], src.shape[4], int(k), int(stride), int(pad))
-    fl = {WRW_KERNEL_WINO43: fq // 2, WRW_KERNEL_WINO23: fq * 2 // 3, WRW_KERNEL_S3: 6 * fq}.get(kid, fq)
+    acct = _kernel_accounting("wrw", (g.data_ptr() % 16, src.data_ptr() % 16), *geo)
     if torch.are_deterministic_algorithms_enabled():
-        return _conv3d_wrw_det(g, src.data_ptr(), None, None, geo, 4 * (g.numel() + src.numel()), fl, fq,
-                               kernel=_wrw_s3_symbol(kid, Cg, g.shape[4]))
+        return _conv3d_wrw_det(g, src.data_ptr(), None, None, geo, 4 * (g.numel() + src.numel()), acct)
     dw = _dw_zeros(g, (Cg, Cs, k, k, k))
+    sym, fl, fq = acct
     with torch.cuda.device(g.device):
-        _call("fs_conv3d_wrw", g.data_ptr(), src.data_ptr(), dw.data_ptr(), B, Cg, Cs, g.shape[2],
-              g.shape[3], g.shape[4], src.shape[2], src.shape[3], src.shape[4], int(k), int(stride),
-              int(pad), _stream(g), algo_bytes=4 * (g.numel() + src.numel()),
-              algo_flops=fl, equiv_flops=fq,
-              kernel="conv3d_wrw_wino4_kernel<0>" if kid == WRW_KERNEL_WINO43 else _wrw_s3_symbol(kid, Cg, g.shape[4]))
+        _call("fs_conv3d_wrw", g.data_ptr(), src.data_ptr(), dw.data_ptr(), *geo, _stream(g),
+              algo_bytes=4 * (g.numel() + src.numel()), algo_flops=fl, equiv_flops=fq, kernel=sym)
     return dw
-
-
-def _wrw_s3_symbol(kid, Cg, Wo):
-    """Kernel symbol of a weight-gradient call that runs on split-bf16 matrix cores (csrc/convwrw_s3.hpp): its launch
-    records carry the EXECUTED flops (six bf16 products per fp32 multiply-add), priced against the bf16 peak; else None."""
-    if kid != WRW_KERNEL_S3:
-        return None
-    if int(Cg) > 32:
-        return "conv3d_wrw_s3_kernel<8, 2, 1, 2, 4, 0, %d>" % (16 if int(Wo) == 16 else 32)
-    return "conv3d_wrw_s3_kernel<6, 1, 2, 2, 3, 0, 32>"
 
 
 WRW_KERNEL_BRICK, WRW_KERNEL_DMA, WRW_KERNEL_WINO23, WRW_KERNEL_WINO43, WRW_KERNEL_S3 = 0, 1, 2, 3, 4  # include/flowsci_hip.h FS_WRW_KERNEL_*
@@ -1837,9 +1805,8 @@ WRW_KERNEL_BRICK, WRW_KERNEL_DMA, WRW_KERNEL_WINO23, WRW_KERNEL_WINO43, WRW_KERN
 def conv3d_wrw_kernel_id(g_ptr, src_ptr, B, Cg, Cs, g_dhw, src_dhw, k, stride, pad):
     """The kernel fs_conv3d_wrw dispatches this call to (WRW_KERNEL_*): the library's own answer
     (fs_conv3d_wrw_kernel_id; nothing is launched, the pointers are inspected for alignment only)."""
-    kid = int(_lib.lib().fs_conv3d_wrw_kernel_id(int(g_ptr), int(src_ptr), int(B), int(Cg), int(Cs),
-                                                 *(int(v) for v in g_dhw), *(int(v) for v in src_dhw), int(k), int(stride),
-                                                 int(pad)))
+    kid = _plan("wrw", (int(g_ptr) % 16, int(src_ptr) % 16),
+                tuple(int(v) for v in (B, Cg, Cs, *g_dhw, *src_dhw, k, stride, pad)))[0]
     if kid < 0:
         _lib.check(-kid, "fs_conv3d_wrw_kernel_id")
     return kid
@@ -1902,13 +1869,16 @@ def conv3d_fwd_prelu_ms(pieces, w, bias, prelu_weight, k, stride, pad):
         return None
     y = x0.new_empty((B, Cout, Do, Ho, Wo))
     z = torch.empty_like(y)
-    wp, ws = _prepared_fwd(w, x0.data_ptr(), B, Cin, Cout, (Di, Hi, Wi), (Do, Ho, Wo), k, stride, pad, 0)
+    geo = (B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, int(k), int(stride), int(pad), 0)
+    wp, ws = _prepared_fwd(w, x0.data_ptr(), geo)
+    # (the multi-source dispatch is the single-tensor one's for the same shape; the first plane stands for the alignment)
+    sym, fl, fq = _kernel_accounting("fwd", (x0.data_ptr() % 16,), *geo)
     xbytes = 4 * B * Cin * Di * Hi * Wi
     with torch.cuda.device(x0.device):
-        rc = _call_rc("fs_conv3d_fwd_prelu_ms", pv, sv, wp, _ptr(bias), a.data_ptr(), y.data_ptr(), z.data_ptr(),
+        rc = _call("fs_conv3d_fwd_prelu_ms", pv, sv, wp, _ptr(bias), a.data_ptr(), y.data_ptr(), z.data_ptr(),
                    ws.data_ptr(), B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, int(k), int(stride), int(pad), int(a.numel()),
-                      _stream(x0), algo_bytes=xbytes + 8 * y.numel(), algo_flops=2 * y.numel() * Cin * int(k) ** 3,
-                      record_as="fs_conv3d_fwd", allow=(FS_ERR_UNSUPPORTED,))
+                   _stream(x0), algo_bytes=xbytes + 8 * y.numel(), algo_flops=fl, equiv_flops=fq, kernel=sym,
+                   record_as="fs_conv3d_fwd", allow=(FS_ERR_UNSUPPORTED,))
     if rc == FS_ERR_UNSUPPORTED:
         _prep_not_written()
         return None
@@ -1924,21 +1894,17 @@ def conv3d_wrw_ms(g, pieces, k, stride, pad):
     g = _need_cuda_f32("g", g, 5)
     B, Cg = g.shape[:2]
     Di, Hi, Wi = pieces[0].shape[2:]
-    fq = 2 * g.numel() * Cs * int(k) ** 3
+    geo = (B, Cg, Cs, g.shape[2], g.shape[3], g.shape[4], Di, Hi, Wi, int(k), int(stride), int(pad))
     # (the multi-source dispatch is the single-tensor one's for the same shape; the first plane stands for the alignment)
-    kid = conv3d_wrw_kernel_id(g.data_ptr(), pieces[0].data_ptr(), B, Cg, Cs, g.shape[2:], (Di, Hi, Wi), k, stride, pad)
-    sym = _wrw_s3_symbol(kid, Cg, g.shape[4])
-    fl = 6 * fq if sym is not None else fq
+    acct = _kernel_accounting("wrw", (g.data_ptr() % 16, pieces[0].data_ptr() % 16), *geo)
     if torch.are_deterministic_algorithms_enabled():
-        geo = (B, Cg, Cs, g.shape[2], g.shape[3], g.shape[4], Di, Hi, Wi, int(k), int(stride), int(pad))
-        return _conv3d_wrw_det(g, 0, pv, sv, geo, 4 * (g.numel() + B * Cs * Di * Hi * Wi), fl, fq, allow_unsupported=True,
-                               kernel=sym)
+        return _conv3d_wrw_det(g, 0, pv, sv, geo, 4 * (g.numel() + B * Cs * Di * Hi * Wi), acct, allow_unsupported=True)
     dw = _dw_zeros(g, (Cg, Cs, k, k, k))
+    sym, fl, fq = acct
     with torch.cuda.device(g.device):
-        rc = _call_rc("fs_conv3d_wrw_ms", g.data_ptr(), pv, sv, dw.data_ptr(), B, Cg, Cs, g.shape[2], g.shape[3], g.shape[4],
-                   Di, Hi, Wi, int(k), int(stride), int(pad), _stream(g),
-                      algo_bytes=4 * (g.numel() + B * Cs * Di * Hi * Wi), algo_flops=fl, equiv_flops=fq, kernel=sym,
-                      record_as="fs_conv3d_wrw", allow=(FS_ERR_UNSUPPORTED,))
+        rc = _call("fs_conv3d_wrw_ms", g.data_ptr(), pv, sv, dw.data_ptr(), *geo, _stream(g),
+                   algo_bytes=4 * (g.numel() + B * Cs * Di * Hi * Wi), algo_flops=fl, equiv_flops=fq, kernel=sym,
+                   record_as="fs_conv3d_wrw", allow=(FS_ERR_UNSUPPORTED,))
     if rc == FS_ERR_UNSUPPORTED:
         return None
     return dw
@@ -1969,25 +1935,17 @@ def conv3d_deconv_grad_input_dprelu(gy, w, act_y, prelu_weight):
     out = torch.empty_like(act_y)
     ga, gb = torch.empty_like(a), act_y.new_empty(Cin_t)
     part = act_y.new_empty(npart)
-    wp, ws = _prepared_fwd(w, gy.data_ptr(), B, Cg, Cin_t, (Di, Hi, Wi), (Do, Ho, Wo), 4, 2, 1, 0)
-    nb = 4 * (gy.numel() + 2 * out.numel())
-    fl = 2 * out.numel() * Cg * 64
+    geo = (B, Cg, Cin_t, Di, Hi, Wi, Do, Ho, Wo, 4, 2, 1, 0)
+    wp, ws = _prepared_fwd(w, gy.data_ptr(), geo)
+    sym, fl, fq = _kernel_accounting("fwd", (gy.data_ptr() % 16,), *geo)
     with torch.cuda.device(gy.device):
-        args = (gy.data_ptr(), wp, act_y.data_ptr(), a.data_ptr(), a.numel(), out.data_ptr(), ga.data_ptr(),
-                gb.data_ptr(), part.data_ptr(), ws.data_ptr(), B, Cg, Cin_t, Di, Hi, Wi, Do, Ho, Wo, 4, 2, 1, _stream(gy))
-        if _timing is None or (_timing_only is not None and "fs_conv3d_fwd" not in _timing_only):
-            rc = L.fs_conv3d_fwd_dprelu(*args)
-        else:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            rc = L.fs_conv3d_fwd_dprelu(*args)
-            e1.record()
-            if rc == 0:
-                _timing.setdefault("fs_conv3d_fwd", []).append((e0, e1, nb, fl, fl, None))
+        rc = _call("fs_conv3d_fwd_dprelu", gy.data_ptr(), wp, act_y.data_ptr(), a.data_ptr(), a.numel(), out.data_ptr(),
+                   ga.data_ptr(), gb.data_ptr(), part.data_ptr(), ws.data_ptr(), B, Cg, Cin_t, Di, Hi, Wi, Do, Ho, Wo,
+                   4, 2, 1, _stream(gy), algo_bytes=4 * (gy.numel() + 2 * out.numel()), algo_flops=fl, equiv_flops=fq,
+                   kernel=sym, record_as="fs_conv3d_fwd", allow=(FS_ERR_UNSUPPORTED,))
     if rc == FS_ERR_UNSUPPORTED:
         _prep_not_written()
         return None
-    _lib.check(rc, "fs_conv3d_fwd_dprelu")
     return out, ga, gb
 
 
@@ -2014,14 +1972,14 @@ def conv3d_k3_grad_input_dprelu(gy, w, act_y, prelu_weight):
     out = torch.empty_like(act_y)
     ga, gb = torch.empty_like(a), act_y.new_empty(Cx)
     part = act_y.new_empty(npart)
-    wp, ws = _prepared_fwd(w, gy.data_ptr(), B, Cg, Cx, (D, H, W), (D, H, W), 3, 1, 1, 1)
-    macs = _fwd_k3_macs(gy.data_ptr(), B, Cg, Cx, (D, H, W), 1)
+    geo = (B, Cg, Cx, D, H, W, D, H, W, 3, 1, 1, 1)
+    wp, ws = _prepared_fwd(w, gy.data_ptr(), geo)
+    sym, fl, fq = _kernel_accounting("fwd", (gy.data_ptr() % 16,), *geo)
     with torch.cuda.device(gy.device):
-        rc = _call_rc("fs_conv3d_fwd_dprelu", gy.data_ptr(), wp, act_y.data_ptr(), a.data_ptr(), a.numel(),
-                      out.data_ptr(), ga.data_ptr(), gb.data_ptr(), part.data_ptr(), ws.data_ptr(), B, Cg, Cx, D, H, W,
-                      D, H, W, 3, 1, 1, _stream(gy), algo_bytes=4 * (gy.numel() + 2 * out.numel()),
-                      algo_flops=int(2 * out.numel() * Cg * macs), kernel=_fwd_k3_symbol(macs, W),
-                      equiv_flops=2 * out.numel() * Cg * 27, record_as="fs_conv3d_fwd", allow=(FS_ERR_UNSUPPORTED,))
+        rc = _call("fs_conv3d_fwd_dprelu", gy.data_ptr(), wp, act_y.data_ptr(), a.data_ptr(), a.numel(),
+                   out.data_ptr(), ga.data_ptr(), gb.data_ptr(), part.data_ptr(), ws.data_ptr(), B, Cg, Cx, D, H, W,
+                   D, H, W, 3, 1, 1, _stream(gy), algo_bytes=4 * (gy.numel() + 2 * out.numel()), algo_flops=fl,
+                   equiv_flops=fq, kernel=sym, record_as="fs_conv3d_fwd", allow=(FS_ERR_UNSUPPORTED,))
     if rc == FS_ERR_UNSUPPORTED:
         _prep_not_written()
         return None
@@ -2071,16 +2029,11 @@ def conv3d_fwd(x, w, bias, k, stride, pad, wmode=0, prelu_weight=None, addend=No
     if min(Do, Ho, Wo) < 1:
         raise ValueError("convolution output is empty for input %s" % (tuple(x.shape),))
     y = x.new_empty((B, Cout, Do, Ho, Wo))
-    wp, ws = _prepared_fwd(w, x.data_ptr(), B, Cin, Cout, (Di, Hi, Wi), (Do, Ho, Wo), k, stride, pad, wmode)
-    nb, fq = 4 * (x.numel() + y.numel()), 2 * y.numel() * Cin * int(k) ** 3
-    fl, sym = fq, None
-    if int(k) == 3 and int(stride) == 1 and int(pad) == 1:  # the Winograd forms execute fewer multiply-adds
-        macs = _fwd_k3_macs(x.data_ptr(), B, Cin, Cout, (Di, Hi, Wi), wmode)
-        fl, sym = int(2 * y.numel() * Cin * macs), _fwd_k3_symbol(macs, Wi)
-    elif int(k) == 4 and int(stride) == 2 and int(pad) == 1 and not wmode:
-        sym = _fwd_k4_symbol(x.data_ptr(), B, Cin, Cout, (Di, Hi, Wi), (Do, Ho, Wo))
-        if sym is not None:
-            fl = 6 * fq  # matrix-core flops EXECUTED: six bf16 products per fp32 multiply-add (priced against the bf16 peak)
+    geo = (B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, int(k), int(stride), int(pad), int(wmode))
+    wp, ws = _prepared_fwd(w, x.data_ptr(), geo)
+    sym, fl, fq = _kernel_accounting("fwd", (x.data_ptr() % 16,), *geo)
+    acct = dict(algo_flops=fl, equiv_flops=fq, kernel=sym, record_as="fs_conv3d_fwd")
+    nb = 4 * (x.numel() + y.numel())
     if addend is not None:
         addend = _need_cuda_f32("addend", addend, 5)
         if addend.shape != y.shape:
@@ -2089,13 +2042,11 @@ def conv3d_fwd(x, w, bias, k, stride, pad, wmode=0, prelu_weight=None, addend=No
     with torch.cuda.device(x.device):
         if prelu_weight is None and addend is not None:
             _call("fs_conv3d_fwd_add", x.data_ptr(), wp, _ptr(bias), addend.data_ptr(), y.data_ptr(),
-                  ws.data_ptr(), B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, int(k), int(stride), int(pad), int(wmode),
-                  _stream(x), algo_bytes=nb, algo_flops=fl, equiv_flops=fq, record_as="fs_conv3d_fwd", kernel=sym)
+                  ws.data_ptr(), *geo, _stream(x), algo_bytes=nb, **acct)
             return y
         if prelu_weight is None:
-            _call("fs_conv3d_fwd", x.data_ptr(), wp, _ptr(bias), y.data_ptr(), ws.data_ptr(), B, Cin,
-                  Cout, Di, Hi, Wi, Do, Ho, Wo, int(k), int(stride), int(pad), int(wmode), _stream(x),
-                  algo_bytes=nb, algo_flops=fl, equiv_flops=fq, kernel=sym)
+            _call("fs_conv3d_fwd", x.data_ptr(), wp, _ptr(bias), y.data_ptr(), ws.data_ptr(), *geo, _stream(x),
+                  algo_bytes=nb, **acct)
             return y
         if wmode:
             raise ValueError("the fused PReLU epilogue is forward-only (wmode 0)")
@@ -2105,9 +2056,7 @@ def conv3d_fwd(x, w, bias, k, stride, pad, wmode=0, prelu_weight=None, addend=No
         z = torch.empty_like(y)
         _call("fs_conv3d_fwd_prelu", x.data_ptr(), wp, _ptr(bias), a.data_ptr(), _ptr(addend),
               y.data_ptr(), z.data_ptr(), ws.data_ptr(), B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, int(k), int(stride),
-              int(pad),
-              a.numel(), _stream(x), algo_bytes=nb + 4 * y.numel(), algo_flops=fl, equiv_flops=fq, record_as="fs_conv3d_fwd",
-              kernel=sym)
+              int(pad), a.numel(), _stream(x), algo_bytes=nb + 4 * y.numel(), **acct)
     return y, z
 
 
@@ -2139,14 +2088,13 @@ def conv3d_tr(x, w, bias, out_dhw=None, prelu_weight=None, addend=None):
         raise ValueError("fs_conv3d_tr supports up to 32 output channels or 64 / 96 / 128, got %d" % Cout)
     L = _lib.lib()
     has_z = int(prelu_weight is not None)
-    wp, ws = _prepared(w, nws, ("tr", B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, has_z, x.data_ptr() % 16),
+    geo = (B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, has_z)
+    wp, ws = _prepared(w, nws, ("tr",) + geo + (x.data_ptr() % 16,),
                        lambda jobs, cap, slab: L.fs_conv3d_tr_wprep_jobs(jobs, cap, x.data_ptr(), w.data_ptr(),
-                                                                        slab.data_ptr(), B, Cin, Cout, Di, Hi, Wi, Do, Ho,
-                                                                        Wo, has_z))
-    nb, fq = 4 * (x.numel() + y.numel()), 2 * x.numel() * Cout * 64
-    sym = _tr_symbol(x.data_ptr(), B, Cin, Cout, (Di, Hi, Wi), (Do, Ho, Wo), has_z)
-    # matrix-core flops EXECUTED: six bf16 products per fp32 multiply-add on the split-bf16 kernels (32 / 16 channel rows)
-    fl = fq if sym is None else 6 * 2 * x.numel() * (32 * ((Cout + 31) // 32) if sym.endswith("<false>") else 16) * 64
+                                                                        slab.data_ptr(), *geo))
+    sym, fl, fq = _kernel_accounting("tr", (x.data_ptr() % 16,), *geo)
+    acct = dict(algo_flops=fl, equiv_flops=fq, kernel=sym, record_as="fs_conv3d_tr")
+    nb = 4 * (x.numel() + y.numel())
     with torch.cuda.device(x.device):
         if addend is not None:
             if prelu_weight is not None:
@@ -2156,11 +2104,11 @@ def conv3d_tr(x, w, bias, out_dhw=None, prelu_weight=None, addend=None):
                 raise ValueError("addend %s must have the output shape %s" % (tuple(addend.shape), tuple(y.shape)))
             _call("fs_conv3d_tr_add", x.data_ptr(), wp, _ptr(bias), addend.data_ptr(), y.data_ptr(),
                   ws.data_ptr(), B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, _stream(x), algo_bytes=nb + 4 * y.numel(),
-                  algo_flops=fl, equiv_flops=fq, record_as="fs_conv3d_tr", kernel=sym)
+                  **acct)
             return y
         if prelu_weight is None:
             _call("fs_conv3d_tr", x.data_ptr(), wp, _ptr(bias), y.data_ptr(), ws.data_ptr(), B, Cin,
-                  Cout, Di, Hi, Wi, Do, Ho, Wo, _stream(x), algo_bytes=nb, algo_flops=fl, equiv_flops=fq, kernel=sym)
+                  Cout, Di, Hi, Wi, Do, Ho, Wo, _stream(x), algo_bytes=nb, **acct)
             return y
         a = _need_cuda_f32("prelu_weight", prelu_weight, 1)
         if a.numel() not in (1, Cout):
@@ -2168,7 +2116,7 @@ def conv3d_tr(x, w, bias, out_dhw=None, prelu_weight=None, addend=None):
         z = torch.empty_like(y)
         _call("fs_conv3d_tr_prelu", x.data_ptr(), wp, _ptr(bias), a.data_ptr(), y.data_ptr(),
               z.data_ptr(), ws.data_ptr(), B, Cin, Cout, Di, Hi, Wi, Do, Ho, Wo, a.numel(), _stream(x),
-              algo_bytes=nb + 4 * y.numel(), algo_flops=fl, equiv_flops=fq, record_as="fs_conv3d_tr", kernel=sym)
+              algo_bytes=nb + 4 * y.numel(), **acct)
     return y, z
 
 
