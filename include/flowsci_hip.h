@@ -472,6 +472,9 @@ int fs_laploss3d_bwd(const float* sgn, const float* grad_loss, float* ws, float*
  * wmode 1: w is [Cin][Cout][k^3] and is applied flipped (tap k^3-1-k): the INPUT GRADIENT of a
  *          stride-1 "same" Conv3d is this convolution of grad_out with the layer's own weight.
  * ws: device scratch of fs_conv3d_fwd_ws_floats(Cin, Cout, kernel) floats (re-laid-out weights).
+ * Alignment: y, and z / addend / residual / grad_act_y / act_y of the variants below, must be 16-byte aligned (the
+ * epilogues move 16 bytes at a time); FS_ERR_ARG otherwise, before anything is launched.  The same holds for y, z and
+ * addend of fs_conv3d_tr*.  x and ws may have any 4-byte alignment (a misaligned one only selects a slower kernel).
  */
 long long fs_conv3d_fwd_ws_floats(int Cin, int Cout, int kernel);
 int fs_conv3d_fwd(const float* x, const float* w, const float* bias, float* y, float* ws,
@@ -486,7 +489,7 @@ int fs_conv3d_fwd(const float* x, const float* w, const float* bias, float* y, f
  * x [B,Cin,Di,Hi,Wi], w [Cin][Cout][4*4*4] (a ConvTranspose3d weight as stored; a Conv3d weight
  * [Cout_conv][Cin_conv][64] reads the same way for its input gradient), bias may be NULL,
  * y [B,Cout,Dout,Hout,Wout] with out = 2*in per axis (or 2*in + 1: input gradient of a convolution
- * whose odd input extent left its last plane unused -- that plane receives zeros).
+ * with an odd input extent -- its last plane is read by tap 3 of the last output, so it is not zero).
  * Cout <= 32 (FS_ERR_ARG otherwise).  ws: fs_conv3d_tr_ws_floats(Cin, Cout) floats of device scratch
  * (0 for Cout <= 6: those run on the vector ALUs with scalar-loaded weights).
  */

@@ -578,6 +578,8 @@ static int conv3d_fwd_impl(const float* x, const float* w, const float* bias, co
   if (plan == nullptr) FS_REQUIRE_PTR(y);
   FS_REQUIRE_PTR(ws);
   if (z != nullptr && (slope == nullptr || (nslope != 1 && nslope != Cout))) return FS_ERR_ARG;
+  // the epilogues store y / z and read addend / act_y 16 bytes at a time (flowsci_hip.h: 16-byte aligned outputs)
+  if ((((uintptr_t)y | (uintptr_t)z | (uintptr_t)addend | (uintptr_t)(dp ? dp->act_y : nullptr)) & 15) != 0) return FS_ERR_ARG;
   if (B < 1 || Cin < 1 || Cout < 1 || Di < 1 || Hi < 1 || Wi < 1 || Do < 1 || Ho < 1 || Wo < 1)
     return FS_ERR_SHAPE;
   if (!((kernel == 3 && stride == 1) || (kernel == 4 && stride == 2)) || pad < 0 || pad >= kernel ||

@@ -1238,6 +1238,8 @@ static int conv3d_tr_slice(const float* x, const float* w, const float* bias, co
 static int conv3d_tr_impl(const float* x, const float* w, const float* bias, const float* slope, int nslope,
                           const float* addend, float* y, float* z, float* ws, int B, int Cin, int Cout, int Di,
                           int Hi, int Wi, int Dout, int Hout, int Wout, fs_stream_t stream, WprepPlan* plan = nullptr) {
+  // the epilogues store y / z and read addend 16 bytes at a time (flowsci_hip.h: 16-byte aligned outputs)
+  if (plan == nullptr && (((uintptr_t)y | (uintptr_t)z | (uintptr_t)addend) & 15) != 0) return FS_ERR_ARG;
   if (Cout <= 32) return conv3d_tr_slice(x, w, bias, slope, nslope, addend, y, z, ws, B, Cin, Cout, Di, Hi, Wi, Dout, Hout,
                                          Wout, stream, 0, 1, plan);
   if (Cout % 32 != 0 || Cout > 128 || Dout < 1 || Hout < 1 || Wout < 1) return FS_ERR_ARG;

@@ -46,6 +46,12 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _aligned16(t):
+    """`t`, or a copy of it when its data does not start on a 16-byte boundary: the convolution epilogues read addend /
+    act_y 16 bytes at a time and refuse anything else (include/flowsci_hip.h)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _in_dhw(inp, flow):
     """Host int[3] with the sampled volume's extent, or None when it equals the flow's."""
     if tuple(inp.shape[2:]) == tuple(flow.shape[2:]):
@@ -1917,7 +1923,7 @@ def conv3d_deconv_grad_input_dprelu(gy, w, act_y, prelu_weight):
     cover the shape -- the caller then runs conv3d_fwd + prelu_backward."""
     gy = _need_cuda_f32("grad_output", gy, 5)
     w = _need_cuda_f32("w", w, 5)
-    act_y = _need_cuda_f32("act_y", act_y, 5)
+    act_y = _aligned16(_need_cuda_f32("act_y", act_y, 5))
     a = _need_cuda_f32("prelu_weight", prelu_weight, 1)
     B, Cg = gy.shape[:2]                      # the strided convolution's input = grad_out: Cg = deconv Cout
     Cin_t = w.shape[0]                        # its output channels = the deconvolution's input channels
@@ -1956,7 +1962,7 @@ def conv3d_k3_grad_input_dprelu(gy, w, act_y, prelu_weight):
     fused kernel does not cover the shape (the caller then runs conv3d_fwd wmode 1 + prelu_backward)."""
     gy = _need_cuda_f32("grad_output", gy, 5)
     w = _need_cuda_f32("w", w, 5)
-    act_y = _need_cuda_f32("act_y", act_y, 5)
+    act_y = _aligned16(_need_cuda_f32("act_y", act_y, 5))
     a = _need_cuda_f32("prelu_weight", prelu_weight, 1)
     B, Cg = gy.shape[:2]
     Cx = w.shape[1]                           # the gradient's channels = the convolution's input channels
@@ -2035,7 +2041,7 @@ def conv3d_fwd(x, w, bias, k, stride, pad, wmode=0, prelu_weight=None, addend=No
     acct = dict(algo_flops=fl, equiv_flops=fq, kernel=sym, record_as="fs_conv3d_fwd")
     nb = 4 * (x.numel() + y.numel())
     if addend is not None:
-        addend = _need_cuda_f32("addend", addend, 5)
+        addend = _aligned16(_need_cuda_f32("addend", addend, 5))
         if addend.shape != y.shape:
             raise ValueError("addend %s must have the output shape %s" % (tuple(addend.shape), tuple(y.shape)))
         nb += 4 * y.numel()
@@ -2099,7 +2105,7 @@ def conv3d_tr(x, w, bias, out_dhw=None, prelu_weight=None, addend=None):
         if addend is not None:
             if prelu_weight is not None:
                 raise ValueError("addend and prelu_weight are mutually exclusive")
-            addend = _need_cuda_f32("addend", addend, 5)
+            addend = _aligned16(_need_cuda_f32("addend", addend, 5))
             if addend.shape != y.shape:
                 raise ValueError("addend %s must have the output shape %s" % (tuple(addend.shape), tuple(y.shape)))
             _call("fs_conv3d_tr_add", x.data_ptr(), wp, _ptr(bias), addend.data_ptr(), y.data_ptr(),
