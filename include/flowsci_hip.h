@@ -45,8 +45,9 @@ enum {
  *        The library reads no environment variable any more (measurement switches live in the -DFS_ABLATION build).
  *   330  round 5: fs_warp3d_kernel_id (which kernel a trilinear-warp call dispatches to; nothing launched).
  *   340  fs_frame_metrics2d / fs_frame_metrics3d and their _ws_bytes queries (sequence evaluation: PSNR / SSIM).
- *   350  fs_flow_metrics2d / fs_flow_metrics3d and their _ws_bytes queries (flow accuracy: EPE, Fl, angular error). */
-#define FS_ABI_VERSION 350
+ *   350  fs_flow_metrics2d / fs_flow_metrics3d and their _ws_bytes queries (flow accuracy: EPE, Fl, angular error).
+ *   360  fs_triplet_gather, fs_series_stats / fs_series_stats_ws_bytes (training batches from a device-resident series). */
+#define FS_ABI_VERSION 360
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -700,6 +701,47 @@ int fs_flow_metrics2d(const float* pred, const float* gt, int N, int C, int H, i
 int fs_flow_metrics3d(const float* pred, const float* gt, int N, int C, int D, int H, int W, long long pred_bstride,
                       long long gt_bstride, const unsigned char* valid, const unsigned char* noc, int convention,
                       float tau_abs, float tau_rel, float* epe_map, double* ws, double* out, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,
+ * np.float32, append flipped copies, cut (img0, img1, gt) triplets) and the host-to-device copy of Flow-3D/train.py:144,
+ * as one launch per batch over an array that stays on the device in its stored type.
+ *   base: `n_elems` elements of `dtype` (FS_SERIES_*: uint8, uint16, IEEE half, float), frames of Ds x Hs x Ws
+ *     elements (Ds = 1 for the 2-D models) anywhere inside it.
+ *   jobs: B records in DEVICE memory (8-byte aligned), one per sample:
+ *     off[3]     element offsets inside base of the frames written to channels 0, 1, 2 (img0, img1, gt): t*Ds*Hs*Ws
+ *                for a series [T,D,H,W], (3n + c)*Ds*Hs*Ws for ready-made triplets [N,3,D,H,W]
+ *     z0, y0, x0 crop origin
+ *     flip       bit 0: mirror along W, bit 1: along H, bit 2: along D -- of the cropped block:
+ *                out[z,y,x] = frame[z0 + (flip & 4 ? Do-1-z : z), y0 + (flip & 2 ? Ho-1-y : y), x0 + (flip & 1 ? Wo-1-x : x)]
+ *     lo, inv    out = (v - lo) * inv, two separately rounded fp32 operations (no FMA)
+ *   out: fp32 [B,3,Do,Ho,Wo], contiguous.
+ *   v is the stored value converted exactly to fp32; a non-finite v (NaN, +-inf) becomes 0 before the normalisation
+ *   (the reference's np.nan_to_num maps +-inf to +-FLT_MAX instead: a deliberate divergence).
+ *   The library cannot read the records, so the kernel checks them: a source coordinate outside the frame, or an
+ *   element index outside [0, n_elems), reads as 0 -- no record makes the kernel touch memory outside base.
+ *   FS_ERR_SHAPE: B or an extent < 1, a crop larger than the frame, a frame larger than the array, more than 2^31-1
+ *   output elements per channel; FS_ERR_ARG: an unknown dtype, base not aligned to its element, jobs to 8 bytes.
+ *
+ * fs_series_stats: for each of T consecutive frames of frame_elems elements, out[t] = {minimum over the finite
+ *   elements (+inf if none), maximum (-inf if none), number of non-finite elements} as fp64 (every value of the four
+ *   types and every count below 2^53 is exact).  Partials per workgroup in `ws` (fs_series_stats_ws_bytes bytes, 8-byte
+ *   aligned), combined by a second launch in a fixed order: no atomics.  FS_ERR_SHAPE: T < 1 or > 2^22, frame_elems < 1
+ *   or > 2^40.  The _ws_bytes query launches nothing and returns the byte count or -(FS_ERR_*).
+ */
+enum { FS_SERIES_U8 = 0, FS_SERIES_U16 = 1, FS_SERIES_F16 = 2, FS_SERIES_F32 = 3 };
+typedef struct FsTripletJob {
+  long long off[3];
+  int z0, y0, x0;
+  unsigned flip;
+  float lo, inv;
+  int reserved[4];
+} FsTripletJob; /* 64 bytes */
+int fs_triplet_gather(const void* base, int dtype, long long n_elems, int Ds, int Hs, int Ws, const FsTripletJob* jobs,
+                      int B, int Do, int Ho, int Wo, float* out, fs_stream_t stream);
+long long fs_series_stats_ws_bytes(int T, long long frame_elems);
+int fs_series_stats(const void* base, int dtype, int T, long long frame_elems, double* ws, double* out,
+                    fs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -157,11 +157,33 @@ def _dataset(name, frames, size, seed):
 DATASETS = {2: ("rectangle2d", "droplet2d"), 3: ("droplet3d", "jets3d")}
 
 
+def _load_seq(path, nd, normalize="none"):
+    """--seq FILE through data.series.load_series (.npy / .npz; uint8, uint16, float16, float32 or float64) as fp32
+    [T,*sp]; a file of ready-made triplets or of another rank is refused.  normalize 'none' passes the values through
+    as stored; 'global' / 'frame' read non-finite values as 0 and map the file's / each frame's range to [0,1]."""
+    from .data.series import load_series, series_layout
+    arr = load_series(path, nd=nd)
+    if series_layout(arr.shape, nd)[0] != "series":
+        raise ValueError("--seq takes a series [T,%s], got ready-made triplets %s" % (",".join("DHW"[3 - nd:]), arr.shape))
+    arr = np.asarray(arr).astype(np.float32)
+    if arr.ndim == nd + 2 and arr.shape[1] == 1:
+        arr = arr[:, 0]
+    if normalize != "none":
+        arr[~np.isfinite(arr)] = 0.0
+        ax = None if normalize == "global" else tuple(range(1, arr.ndim))
+        lo, hi = arr.min(axis=ax, keepdims=True), arr.max(axis=ax, keepdims=True)
+        arr = (arr - lo) / np.where(hi > lo, hi - lo, np.float32(1))
+    return torch.from_numpy(arr)
+
+
 def main(Model, nd, argv=None):
     ap = argparse.ArgumentParser(description="interpolate a time series from every factor-th frame and score it")
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--dataset", choices=DATASETS[nd], help="synthetic sequence")
     src.add_argument("--seq", help=".npy sequence [T,%s] in [0,1]" % ",".join("DHW"[3 - nd:]))
+    ap.add_argument("--normalize", choices=("global", "frame", "none"), default="none",
+                    help="--seq: map the stored values to [0,1] by the range of the file / of each frame (default: "
+                         "the file is in [0,1] already)")
     ap.add_argument("--frames", type=int, default=17, help="frames of a synthetic sequence")
     ap.add_argument("--size", type=int, nargs="+", default=None, help="synthetic extent (S, or H W in 2-D)")
     ap.add_argument("--seed", type=int, default=1234)
@@ -179,7 +201,7 @@ def main(Model, nd, argv=None):
         print("no flownet.pkl under %s: using random-init weights" % args.model)
     model.eval()
     if args.seq:
-        seq = torch.from_numpy(np.load(args.seq).astype(np.float32))
+        seq = _load_seq(args.seq, nd, args.normalize)
         name = os.path.basename(args.seq)
     else:
         seq = _dataset(args.dataset, args.frames, args.size, args.seed)

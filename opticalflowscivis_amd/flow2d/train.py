@@ -9,5 +9,5 @@ if __name__ == "__main__":
     p = add_common_args(argparse.ArgumentParser(), 2)
     p.add_argument('--exp', default=1, type=int)
     args = p.parse_args()
-    assert args.dataset is not None
+    assert args.dataset is not None or args.series is not None
     run(args, Model, 2)

@@ -7,5 +7,5 @@ from .model.RIFE import Model
 
 if __name__ == "__main__":
     args = add_common_args(argparse.ArgumentParser(), 3).parse_args()
-    assert args.dataset is not None
+    assert args.dataset is not None or args.series is not None
     run(args, Model, 3)

@@ -2441,3 +2441,135 @@ def _flow_stats(out, split, emap):
     if emap is not None:
         res["epe_map"] = emap
     return res
+
+
+# --------------------------------------------------------------------------------------------
+# Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
+# --------------------------------------------------------------------------------------------
+import numpy as _np
+
+SERIES_DTYPES = {torch.uint8: 0, torch.uint16: 1, torch.float16: 2, torch.float32: 3}  # FS_SERIES_*
+# include/flowsci_hip.h `FsTripletJob`: one 64-byte record per sample
+TRIPLET_JOB = _np.dtype([("off", "<i8", (3,)), ("z0", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("flip", "<u4"),
+                         ("lo", "<f4"), ("inv", "<f4"), ("reserved", "<i4", (4,))])
+assert TRIPLET_JOB.itemsize == 64
+
+
+def triplet_gather_cost(batch, crop, itemsize):
+    """(HBM bytes, flops) one triplet_gather needs: three frames' crops read once in the stored type, the fp32 tensor
+    written once; a subtract and a multiply per element."""
+    n = 3 * int(batch)
+    for s in crop:
+        n *= int(s)
+    return n * (int(itemsize) + 4), 2 * n
+
+
+def _stored_operand(stored):
+    if not isinstance(stored, torch.Tensor):
+        raise ValueError("stored must be a tensor")
+    if stored.dtype not in SERIES_DTYPES:
+        raise ValueError("stored must be uint8, uint16, float16 or float32, got %s" % stored.dtype)
+    if not stored.is_cuda:
+        raise ValueError("stored must live on a GPU (the HIP hot path has no CPU fallback); got %s" % stored.device)
+    if not stored.is_contiguous():
+        raise ValueError("stored must be contiguous")
+    return stored
+
+
+def check_triplet_jobs(jobs, n_elems, frame, crop):
+    """Host-side validation of a plan (numpy records of TRIPLET_JOB) against a stored array of `n_elems` elements with
+    frames of `frame` = (Ds, Hs, Ws), cropped to `crop` = (Do, Ho, Wo): every frame inside the array, every crop inside
+    its frame, known flip bits, finite normalisation.  ValueError names the first offending record."""
+    jobs = _np.asarray(jobs)
+    if jobs.dtype != TRIPLET_JOB or jobs.ndim != 1:
+        raise ValueError("jobs must be a 1-D numpy array of ops.TRIPLET_JOB records")
+    F = int(frame[0]) * int(frame[1]) * int(frame[2])
+    bad = ((jobs["off"] < 0) | (jobs["off"] > n_elems - F)).any(axis=1)
+    for k, (f, c) in zip(("z0", "y0", "x0"), zip(frame, crop)):
+        bad |= (jobs[k] < 0) | (jobs[k] > int(f) - int(c))
+    bad |= jobs["flip"] > 7
+    bad |= ~(_np.isfinite(jobs["lo"]) & _np.isfinite(jobs["inv"]))
+    if bad.any():
+        i = int(_np.flatnonzero(bad)[0])
+        raise ValueError("triplet job %d leaves the stored array (%d elements, frames %s, crop %s) or is malformed: %r"
+                         % (i, n_elems, tuple(frame), tuple(crop), jobs[i]))
+    return jobs
+
+
+def upload_triplet_jobs(jobs, stored, crop, checked=False):
+    """Validate numpy TRIPLET_JOB records against `stored` (frames = its trailing len(crop) axes) and copy them to its
+    device in one transfer: an int64 [n, 8] tensor, one row per record, of which triplet_gather takes slices.
+    checked=True: the caller has run check_triplet_jobs on these records against this array already."""
+    stored = _stored_operand(stored)
+    frame, crop3 = _series_frame(stored, crop)
+    if not checked:
+        jobs = check_triplet_jobs(jobs, stored.numel(), frame, crop3)
+    host = torch.from_numpy(_np.ascontiguousarray(jobs).view("<i8").reshape(-1, 8))
+    return host.to(stored.device)
+
+
+def _series_frame(stored, crop):
+    nd = len(crop)
+    if nd not in (2, 3) or stored.dim() < nd + 1:
+        raise ValueError("crop must have 2 or 3 extents and stored at least one more axis, got crop %s, stored %s" %
+                         (tuple(crop), tuple(stored.shape)))
+    frame = (1,) * (3 - nd) + tuple(int(s) for s in stored.shape[-nd:])
+    crop3 = (1,) * (3 - nd) + tuple(int(s) for s in crop)
+    if any(c < 1 or c > f for c, f in zip(crop3, frame)):
+        raise ValueError("crop %s does not fit frames of %s" % (tuple(crop), frame[3 - nd:]))
+    return frame, crop3
+
+
+def triplet_gather(stored, jobs, out_shape, out=None):
+    """One training batch [B,3,*crop] (fp32; channels img0, img1, gt) out of a stored series on the GPU, one launch
+    (fs_triplet_gather): per sample a TRIPLET_JOB record names three frames, a crop origin, mirrors and (lo, inv);
+    out = (float(v) - lo) * inv with non-finite v read as 0.
+
+    stored: contiguous uint8 / uint16 / float16 / float32 GPU tensor whose trailing 3 (2) axes are a frame.
+    jobs: numpy TRIPLET_JOB records (validated here, then uploaded), or rows of the tensor upload_triplet_jobs
+    returned (validated there; nothing is copied or synchronised).  An int64 [B,8] tensor from anywhere else is NOT
+    validated -- it is device memory -- only guarded: the kernel reads 0 wherever such a record leaves the frame or
+    the array.  out_shape: (B, 3, Do, Ho, Wo) or (B, 3, Ho, Wo)."""
+    stored = _stored_operand(stored)
+    out_shape = tuple(int(s) for s in out_shape)
+    if len(out_shape) not in (4, 5) or out_shape[1] != 3 or out_shape[0] < 1:
+        raise ValueError("out_shape must be (B,3,Do,Ho,Wo) or (B,3,Ho,Wo), got %s" % (out_shape,))
+    frame, crop3 = _series_frame(stored, out_shape[2:])
+    B = out_shape[0]
+    if isinstance(jobs, _np.ndarray):
+        jobs = upload_triplet_jobs(jobs, stored, out_shape[2:])
+    if (not isinstance(jobs, torch.Tensor) or jobs.dtype != torch.int64 or jobs.dim() != 2 or jobs.shape[1] != 8 or
+            not jobs.is_contiguous() or jobs.device != stored.device):
+        raise ValueError("jobs must be numpy TRIPLET_JOB records or a contiguous int64 [B,8] tensor on stored's device")
+    if jobs.shape[0] != B:
+        raise ValueError("%d job records for a batch of %d" % (jobs.shape[0], B))
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.float32, device=stored.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != out_shape or
+          not out.is_contiguous() or out.device != stored.device):
+        raise ValueError("out must be a contiguous float32 %s tensor on stored's device" % (out_shape,))
+    nbytes, flops = triplet_gather_cost(B, crop3, stored.element_size())
+    with torch.cuda.device(stored.device):
+        _call("fs_triplet_gather", stored.data_ptr(), SERIES_DTYPES[stored.dtype], stored.numel(), *frame,
+              jobs.data_ptr(), B, *crop3, out.data_ptr(), _stream(stored), algo_bytes=nbytes, algo_flops=flops)
+    return out
+
+
+def series_stats(stored):
+    """Per frame stored[t] (uint8 / uint16 / float16 / float32 on a GPU, contiguous): an fp64 [T,3] tensor of the
+    minimum and maximum over its finite elements (+inf / -inf if none) and the count of non-finite elements
+    (fs_series_stats: two deterministic launches, nothing synchronised)."""
+    stored = _stored_operand(stored)
+    if stored.dim() < 2 or stored.numel() == 0:
+        raise ValueError("stored must be [T, ...] with at least one element, got %s" % (tuple(stored.shape),))
+    T = int(stored.shape[0])
+    F = stored.numel() // T
+    nb = _lib.lib().fs_series_stats_ws_bytes(T, F)
+    if nb < 0:
+        _lib.check(int(-nb), "fs_series_stats_ws_bytes")
+    ws = torch.empty(nb // 8, dtype=torch.float64, device=stored.device)
+    out = torch.empty(T, 3, dtype=torch.float64, device=stored.device)
+    with torch.cuda.device(stored.device):
+        _call("fs_series_stats", stored.data_ptr(), SERIES_DTYPES[stored.dtype], T, F, ws.data_ptr(), out.data_ptr(),
+              _stream(stored), algo_bytes=stored.numel() * stored.element_size())
+    return out

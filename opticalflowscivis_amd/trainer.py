@@ -2,8 +2,9 @@
 
 Mirrors Flow-2D/train.py:70-553 and Flow-3D/train.py:72-478 (same flags, LR schedule, per-epoch
 evaluation with PSNR, rank-0 checkpointing, one barrier per epoch) with two deliberate changes:
-  * data: seeded synthetic stand-ins (data/synthetic.py) -- the reference's pickles are not in
-    its tree and there is no network;
+  * data: `--series FILE` trains on the user's own stored time series (data/series.py: the reference's
+    `load_data`, with the array resident on the GPU and batches assembled there); without it, seeded
+    synthetic stand-ins (data/synthetic.py) -- the reference's pickles are not in its tree;
   * sharding: `DistributedSampler(shuffle=True)` + `set_epoch` is ON.  The reference left it
     commented out (Flow-3D/train.py:82-83,139; Flow-2D/train.py:88-89,137), so under
     torch.distributed every rank trained on the same samples.
@@ -19,6 +20,7 @@ from torch.utils.data import DataLoader, Dataset
 from torch.utils.data.distributed import DistributedSampler
 
 from .data import synthetic
+from .data.series import DeviceSeriesLoader, FileTriplets, TripletPlan, load_series
 
 
 class SyntheticTriplets(Dataset):
@@ -161,6 +163,40 @@ class DevicePrefetcher:
             yield batch
 
 
+def series_sets(args, nd, seed):
+    """(train, validation) FileTriplets of `--series FILE [--val_series FILE]`: the validation set is a second file or
+    the frames (items) from --val_from on (default: the last sixth, cut at a multiple of 3 -- the reference's
+    750 / 150 split of 900 frames, Flow-3D/load_datasets.py:138-139)."""
+    arr = load_series(args.series, args.series_key, args.allow_pickle, nd)
+    crop = args.crop
+    if crop is not None:
+        if len(crop) not in (1, nd):
+            raise ValueError("--crop takes one extent or %d, got %s" % (nd, crop))
+        crop = tuple(crop) * nd if len(crop) == 1 else tuple(crop)
+    kw = dict(gap=args.gap, stride=args.stride, crop=crop, normalize=args.normalize, seed=seed)
+    if args.val_series:
+        varr = load_series(args.val_series, args.series_key, args.allow_pickle, nd)
+        tplan = TripletPlan(arr.shape, nd, augment=args.augment, **kw)
+        vplan = TripletPlan(varr.shape, nd, train=False, **kw)
+    else:
+        varr, n = arr, int(arr.shape[0])
+        vfrom = args.val_from if args.val_from is not None else (n - n // 6) // 3 * 3
+        tplan = TripletPlan(arr.shape, nd, stop=vfrom, augment=args.augment, **kw)
+        vplan = TripletPlan(arr.shape, nd, first=vfrom, train=False, **kw)
+    if nd == 3 and len(set(tplan.crop)) != 1:
+        raise ValueError("Flow-3D trains on cubic volumes only (its warp rotates axes): frames of %s need --crop S "
+                         "with one extent, got crop %s" % (tplan.frame, tplan.crop))
+    return FileTriplets(arr, tplan), FileTriplets(varr, vplan)
+
+
+def share_norm_range(train_set, val_set, args):
+    """Under --normalize global a validation FILE is scaled by the training file's range, on every data path."""
+    if args.normalize == "global" and val_set.arr is not train_set.arr:
+        train_set.records()  # (the host loaders' path computes the file's range here)
+        val_set.plan.norm_range = train_set.plan.global_range()
+        val_set.invalidate()
+
+
 def get_learning_rate(step, total_steps):
     """Flow-3D/train.py:50-56: linear warm-up to 3e-4 over 2000 steps, then cosine to 3e-5."""
     if step < 2000:
@@ -211,10 +247,28 @@ def run(args, Model, nd):
     torch.manual_seed(seed)
     model = Model(local_rank if distributed else -1, device=device)
     size = tuple(args.size) if nd == 2 else (args.size[0],) * 3
-    train_set = SyntheticTriplets(args.dataset, args.samples, size, seed)
-    val_set = SyntheticTriplets(args.dataset, max(args.batch_size, args.samples // 8), size, seed + 10 ** 6)
+    from_file = getattr(args, "series", None) is not None
+    if from_file:
+        if args.dataset is not None:
+            raise ValueError("--series and a synthetic --dataset are alternatives: give one")
+        train_set, val_set = series_sets(args, nd, seed)
+        args.dataset = "series"  # (Flow-2D: a name outside _FLOW_GT_DATASETS -- plain frames, no packed flow)
+    else:
+        train_set = SyntheticTriplets(args.dataset, args.samples, size, seed)
+        val_set = SyntheticTriplets(args.dataset, max(args.batch_size, args.samples // 8), size, seed + 10 ** 6)
     sampler = DistributedSampler(train_set, num_replicas=world, rank=rank, shuffle=True) if distributed else None
-    if args.host_data and getattr(args, "host_cache", False):
+    if from_file and not args.host_data:
+        # the stored arrays live on the GPU in their stored type; a batch is one fs_triplet_gather launch
+        train_data = DeviceSeriesLoader(train_set, args.batch_size, device, sampler=sampler, shuffle=True,
+                                        drop_last=True, seed=seed)
+        same = val_set.arr is train_set.arr
+        if same:
+            val_set.plan.stats = train_set.plan.stats
+        val_data = DeviceSeriesLoader(val_set, args.batch_size, device, stored=train_data.stored if same else None)
+    elif args.host_data and getattr(args, "host_cache", False):
+        if from_file and (args.augment == "full" or tuple(train_set.plan.crop) != tuple(train_set.plan.frame)):
+            raise ValueError("--host_cache materialises every item once, so it cannot redraw crops or the 'full' "
+                             "augmentation per epoch: use --host_data alone, or the whole frame with --augment ref|none")
         # the reference's arrangement at volume sizes: the training set resident in host memory, batches gathered into
         # pinned staging buffers, the H2D copy of the next batch on a side stream under the current step
         train_data = DevicePrefetcher(HostCachedLoader(train_set, args.batch_size, device, sampler=sampler, shuffle=True,
@@ -232,6 +286,8 @@ def run(args, Model, nd):
         train_data = DeviceTripletLoader(train_set, args.batch_size, device, sampler=sampler, shuffle=True,
                                          drop_last=True, seed=seed)
         val_data = DeviceTripletLoader(val_set, args.batch_size, device)
+    if from_file:
+        share_norm_range(train_set, val_set, args)
     steps_per_epoch = len(train_data)
     log_path = args.log_path
     os.makedirs(log_path, exist_ok=True)
@@ -262,6 +318,8 @@ def run(args, Model, nd):
     for epoch in range(args.epoch):
         if sampler is not None:
             sampler.set_epoch(epoch)
+        if from_file:
+            train_set.set_epoch(epoch)  # this epoch's crops and draws
         t0 = te = time.time()
         for i, data in enumerate(train_data):
             data = data.to(device, non_blocking=True)  # (already there on both data paths)
@@ -285,7 +343,7 @@ def run(args, Model, nd):
             dt = time.time() - te
             print("epoch %d train loop: %d steps in %.2f s = %.1f ms/step = %.2f pairs/s per rank (%s data, %s)" % (
                 epoch, steps_per_epoch, dt, dt / steps_per_epoch * 1e3, steps_per_epoch * args.batch_size / dt,
-                "host" if args.host_data else "device-generated", "hip-graph replay" if use_graph else "eager launches"))
+                "host" if args.host_data else "device-resident series" if from_file else "device-generated", "hip-graph replay" if use_graph else "eager launches"))
         loss, p, pt = evaluate(model, val_data, nd, args.dataset, device)
         if rank == 0:
             print("eval epoch %d: loss_G %.4e  PSNR %.2f dB  (teacher %.2f dB)" % (epoch, loss, p, pt))
@@ -315,6 +373,24 @@ def add_common_args(parser, nd):
     parser.add_argument('--host_cache', action='store_true',
                         help='with --host_data: keep the whole training set in (pinned) host memory, as the reference\'s '
                              'load_data does, and gather batches from it (no per-sample generation in the loader)')
+    # training on the user's own files (data/series.py)
+    parser.add_argument('--series', default=None, metavar='FILE',
+                        help='train on a stored time series instead of a synthetic --dataset: .npy / .npz / .pkl holding '
+                             '[T,D,H,W], [T,1,D,H,W] or ready-made triplets [N,3,D,H,W] (2-D: without D), kept on the GPU '
+                             'in its stored type (uint8, uint16, float16, float32)')
+    parser.add_argument('--val_series', default=None, metavar='FILE', help='validation file (else: --val_from)')
+    parser.add_argument('--series_key', default=None, help='array name inside an .npz')
+    parser.add_argument('--allow_pickle', action='store_true', help='open a .pkl series (un-pickling executes code)')
+    parser.add_argument('--gap', type=int, default=1, help='triplet = frames (t, t + 2 gap, t + gap)')
+    parser.add_argument('--stride', type=int, default=3, help='distance between the first frames of two triplets')
+    parser.add_argument('--val_from', type=int, default=None, metavar='T',
+                        help='frames (items) from T on are the validation set (default: the last sixth)')
+    parser.add_argument('--augment', choices=('ref', 'none', 'full'), default='ref',
+                        help="ref: the reference's H- and D-mirrored copies, by index; full: plus W mirror and img0/img1 swap")
+    parser.add_argument('--crop', type=int, nargs='+', default=None, metavar='S',
+                        help='random training crop (centre crop in validation): S or D H W, multiples of 32')
+    parser.add_argument('--normalize', choices=('global', 'frame', 'none'), default='global',
+                        help='map the stored values to [0,1] by the range of the file / of each triplet, or leave them')
     parser.add_argument('--eager', action='store_true',
                         help='N = 1: eager launches per step instead of replaying the step from one HIP graph')
     parser.add_argument('--log_every', type=int, default=10)
