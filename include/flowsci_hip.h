@@ -46,8 +46,9 @@ enum {
  *   330  round 5: fs_warp3d_kernel_id (which kernel a trilinear-warp call dispatches to; nothing launched).
  *   340  fs_frame_metrics2d / fs_frame_metrics3d and their _ws_bytes queries (sequence evaluation: PSNR / SSIM).
  *   350  fs_flow_metrics2d / fs_flow_metrics3d and their _ws_bytes queries (flow accuracy: EPE, Fl, angular error).
- *   360  fs_triplet_gather, fs_series_stats / fs_series_stats_ws_bytes (training batches from a device-resident series). */
-#define FS_ABI_VERSION 360
+ *   360  fs_triplet_gather, fs_series_stats / fs_series_stats_ws_bytes (training batches from a device-resident series).
+ *   370  fs_census3d_dist_{fwd,bwd}, fs_flow_smooth3d_{fwd,bwd} (unsupervised flow-side loss terms of Flow-3D). */
+#define FS_ABI_VERSION 370
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -742,6 +743,38 @@ int fs_triplet_gather(const void* base, int dtype, long long n_elems, int Ds, in
 long long fs_series_stats_ws_bytes(int T, long long frame_elems);
 int fs_series_stats(const void* base, int dtype, int T, long long frame_elems, double* ws, double* out,
                     fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Census distance on volumes: the arithmetic of a8 (UPFlow/utils/loss.py:59-71) without the grey conversion, a volume
+ * has one channel.  Zero-padded (2r+1)^3 neighbourhood, u = v[n] - v[c], t = u / sqrt(0.81 + u^2),
+ *   dist[c] = sum over the (2r+1)^3 taps of (t1 - t2)^2 / (0.1 + (t1 - t2)^2).
+ *   vol1, vol2, dist, grad_* [B,1,D,H,W] fp32 contiguous; every extent >= 1 is legal.  radius 1, 2 or 3 (FS_ERR_ARG
+ *   otherwise).  FS_ERR_SHAPE: B * ceil(D / 8) or ceil(H / 16) above 65535.
+ * bwd: grad_vol1 / grad_vol2 (nullable, overwritten) = d sum(grad_dist * dist) / d vol1, vol2; gather-formulated, no
+ * atomics, bit-reproducible.  The loss is fs_robust_sum(dist, ...) as in 2-D.
+ */
+int fs_census3d_dist_fwd(const float* vol1, const float* vol2, float* dist,
+                         int B, int D, int H, int W, int radius, fs_stream_t stream);
+int fs_census3d_dist_bwd(const float* vol1, const float* vol2, const float* grad_dist,
+                         float* grad_vol1, float* grad_vol2,
+                         int B, int D, int H, int W, int radius, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * First-order flow smoothness on volumes (the term Flow-3D/model/RIFE.py:147-167 holds commented out), over pairs of
+ * voxels that both exist, with an optional edge-aware weight:
+ *   sums[0] = sum over b, c, voxel p, axis a in {D,H,W} with p + e_a inside of
+ *             w_a(p) * ((flow[b,c,p+e_a] - flow[b,c,p])^2 + eps^2)^q,
+ *             w_a(p) = exp(-kappa * |guide[b,0,p+e_a] - guide[b,0,p]|);  guide NULL or kappa == 0: w = 1
+ *   sums[1] = the number of (b, c, voxel, axis) pairs counted (exact while it is below 2^24, rounded once above).
+ *   flow [B,C,D,H,W], guide [B,1,D,H,W] (no gradient), sums: 2 device floats, ws: 2*FS_REDUCE_BLOCKS floats.
+ *   Deterministic (per-workgroup partials, fixed-order finish).  FS_ERR_ARG: q <= 0, kappa < 0, eps^2 not a normal
+ *   fp32 number (eps = 0 has no gradient at a zero difference), anything not finite.
+ * bwd: grad_flow (overwritten) = coef[0] * d sums[0] / d flow; every voxel gathers its up to six differences.
+ */
+int fs_flow_smooth3d_fwd(const float* flow, const float* guide, float* sums, float* ws,
+                         int B, int C, int D, int H, int W, float q, float eps, float kappa, fs_stream_t stream);
+int fs_flow_smooth3d_bwd(const float* flow, const float* guide, const float* coef, float* grad_flow,
+                         int B, int C, int D, int H, int W, float q, float eps, float kappa, fs_stream_t stream);
 
 #ifdef __cplusplus
 }

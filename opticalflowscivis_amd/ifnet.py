@@ -161,6 +161,10 @@ class IFNet(nn.Module):
         self.block1 = IFBlock(nd, 5 + fc, c=c1)
         self.block2 = IFBlock(nd, 5 + fc, c=64)
         self.block_tea = IFBlock(nd, 6 + fc, c=64)
+        # Model3D's unsupervised terms need the last student block's two warped frames, which `forward` folds into
+        # merged[2]: with `keep_warped_pair` set, forward leaves them in `warped_pair` (its return value is unchanged)
+        self.keep_warped_pair = False
+        self.warped_pair = None
 
     def forward(self, x, scale=(4, 2, 1), timestep=0.5):
         # channel slices of [B,3,...] are strided: split once into contiguous frames (every warp and
@@ -236,6 +240,7 @@ class IFNet(nn.Module):
             warped_img0, warped_img1 = warped
             flow_list.append(f_dist)
             merged.append((warped_img0, warped_img1))
+        self.warped_pair = merged[2] if self.keep_warped_pair else None
 
         if gt.shape[1] == 1:
             sp = _min_spatial(img0, warped_img0)

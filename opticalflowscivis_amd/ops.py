@@ -1006,6 +1006,111 @@ def census_loss(img1, img1_warp, mask, q, charbonnier_or_abs_robust, if_use_occ,
 
 
 # --------------------------------------------------------------------------------------------
+# the flow-side unsupervised terms of Flow-3D: census distance and first-order smoothness on volumes
+# --------------------------------------------------------------------------------------------
+def _census3d_flops(numel, radius):
+    """Useful flops of one census launch: about 14 per tap (2 rsq, 1 rcp and the multiply-adds around them)."""
+    return 14 * (2 * radius + 1) ** 3 * numel
+
+
+class _Census3DDist(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vol1, vol2, radius):
+        vol1 = _need_cuda_f32("vol1", vol1, 5)
+        vol2 = _need_cuda_f32("vol2", vol2, 5)
+        if vol1.shape != vol2.shape or vol1.shape[1] != 1:
+            raise ValueError("census3d needs two [B,1,D,H,W] volumes, got %s and %s" %
+                             (tuple(vol1.shape), tuple(vol2.shape)))
+        if radius not in (1, 2, 3):
+            raise ValueError("census3d radius must be 1, 2 or 3, got %r" % (radius,))
+        B, _, D, H, W = vol1.shape
+        dist = torch.empty_like(vol1)
+        with torch.cuda.device(vol1.device):
+            _call("fs_census3d_dist_fwd", vol1.data_ptr(), vol2.data_ptr(), dist.data_ptr(), B, D, H, W, radius,
+                  _stream(vol1), algo_bytes=12 * vol1.numel(), algo_flops=_census3d_flops(vol1.numel(), radius))
+        ctx.save_for_backward(vol1, vol2)
+        ctx.radius = radius
+        return dist
+
+    @staticmethod
+    def backward(ctx, gdist):
+        vol1, vol2 = ctx.saved_tensors
+        n1, n2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (n1 or n2):
+            return None, None, None
+        gdist = gdist.contiguous()
+        B, _, D, H, W = vol1.shape
+        g1 = torch.empty_like(vol1) if n1 else None
+        g2 = torch.empty_like(vol2) if n2 else None
+        with torch.cuda.device(vol1.device):
+            _call("fs_census3d_dist_bwd", vol1.data_ptr(), vol2.data_ptr(), gdist.data_ptr(), _ptr(g1), _ptr(g2),
+                  B, D, H, W, ctx.radius, _stream(vol1), algo_bytes=4 * vol1.numel() * (3 + int(n1) + int(n2)),
+                  algo_flops=_census3d_flops(vol1.numel(), ctx.radius))
+        return g1, g2, None
+
+
+def census3d_dist(vol1, vol2, radius=1):
+    """Per-voxel soft Hamming distance between the soft ternary transforms of two [B,1,D,H,W] volumes over the
+    zero-padded (2 radius + 1)^3 neighbourhood (a8's arithmetic, UPFlow/utils/loss.py:59-71), [B,1,D,H,W]."""
+    return _Census3DDist.apply(vol1, vol2, radius)
+
+
+def census3d_loss(vol1, vol2, radius=1, q=0.4):
+    """mean((|dist| + 0.01)^q) over every voxel: a8's robust tail (loss.py:44-48, `photo_loss_use_occ=False`)."""
+    return robust_loss(census3d_dist(vol1, vol2, radius), None, None, PEN_ABS_ROBUST, q, form="mean")
+
+
+class _FlowSmooth3D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flow, guide, q, eps, kappa):
+        flow = _need_cuda_f32("flow", flow, 5)
+        B, C, D, H, W = flow.shape
+        if guide is not None:
+            guide = _need_cuda_f32("guide", guide, 5)
+            if tuple(guide.shape) != (B, 1, D, H, W):
+                raise ValueError("guide must be [B,1,D,H,W] matching flow %s, got %s" %
+                                 (tuple(flow.shape), tuple(guide.shape)))
+        if not (q > 0 and eps > 0 and kappa >= 0):
+            raise ValueError("flow_smooth3d needs q > 0, eps > 0 and kappa >= 0, got %r, %r, %r" % (q, eps, kappa))
+        if flow.numel() == 0:
+            raise ValueError("flow_smooth3d needs a non-empty flow, got %s" % (tuple(flow.shape),))
+        if kappa == 0:
+            guide = None
+        sums = flow.new_empty(2)
+        ws = flow.new_empty(2 * _REDUCE_BLOCKS)
+        nbytes = 4 * (flow.numel() + (0 if guide is None else guide.numel()))
+        with torch.cuda.device(flow.device):
+            _call("fs_flow_smooth3d_fwd", flow.data_ptr(), _ptr(guide), sums.data_ptr(), ws.data_ptr(), B, C, D, H, W,
+                  float(q), float(eps), float(kappa), _stream(flow), algo_bytes=nbytes)
+        # mean over the pairs counted; a flow of one voxel has none and a loss of 0
+        inv = 1.0 / sums[1].clamp(min=1.0)
+        ctx.save_for_backward(flow, guide, inv)
+        ctx.cfg = (float(q), float(eps), float(kappa), nbytes)
+        return sums[0] * inv
+
+    @staticmethod
+    def backward(ctx, gout):
+        flow, guide, inv = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        q, eps, kappa, nbytes = ctx.cfg
+        B, C, D, H, W = flow.shape
+        coef = (gout * inv).reshape(1).contiguous()
+        gflow = torch.empty_like(flow)
+        with torch.cuda.device(flow.device):
+            _call("fs_flow_smooth3d_bwd", flow.data_ptr(), _ptr(guide), coef.data_ptr(), gflow.data_ptr(), B, C, D, H,
+                  W, q, eps, kappa, _stream(flow), algo_bytes=nbytes + 4 * flow.numel())
+        return gflow, None, None, None, None
+
+
+def flow_smooth3d(flow, guide=None, q=0.25, eps=1e-9, kappa=0.0):
+    """First-order smoothness of a [B,C,D,H,W] flow: the mean over channels, voxels p and axes a with p + e_a inside
+    of w_a(p) * ((flow[p + e_a] - flow[p])^2 + eps^2)^q, w_a(p) = exp(-kappa |guide[p + e_a] - guide[p]|)
+    (`guide` [B,1,D,H,W], no gradient; None or kappa = 0: unweighted).  One HIP pass each way."""
+    return _FlowSmooth3D.apply(flow, guide, q, eps, kappa)
+
+
+# --------------------------------------------------------------------------------------------
 # a12: IFNet epilogues
 # --------------------------------------------------------------------------------------------
 class _Merge(torch.autograd.Function):

@@ -1,6 +1,7 @@
 """RIFE `Model` wrapper (optimiser, DDP, update / inference, checkpoints) shared by the Flow-2D
 and Flow-3D entry points.  Mirrors Flow-2D/model/RIFE.py:19-336 and Flow-3D/model/RIFE.py:18-275.
 """
+import collections
 import copy
 import math
 
@@ -162,6 +163,27 @@ class ModelBase:
         return step
 
 
+class UnsupLoss(collections.namedtuple(
+        "UnsupLoss", "photo census smooth census_radius census_q smooth_kappa charb_q charb_eps",
+        defaults=(0., 0., 0., 1, 0.4, 0., 0.25, 1e-9))):
+    """Weights and settings of the flow-side unsupervised terms of `Model3D.update(..., unsup=...)`; a term whose weight
+    is 0 is not computed.
+      photo   Charbonnier ((d^2 + charb_eps^2)^charb_q, the reference's `charbonnier`, Flow-3D/model/RIFE.py:147-148) of
+              each of the last student block's two warped frames against the middle frame, averaged: unlike the L1 on
+              their blend, neither direction can hide behind the mask
+      census  census distance (ops.census3d_loss, patch (2 census_radius + 1)^3, robust exponent census_q) of the same
+              two pairs, averaged
+      smooth  first-order smoothness of the final flow (ops.flow_smooth3d, same Charbonnier), edge-aware with the middle
+              frame as guide when smooth_kappa > 0"""
+    __slots__ = ()
+
+    def __new__(cls, *args, **kwargs):
+        self = super().__new__(cls, *args, **kwargs)
+        if min(self.photo, self.census, self.smooth) < 0 or self.census_radius not in (1, 2, 3) or self.smooth_kappa < 0:
+            raise ValueError("UnsupLoss needs weights >= 0, census_radius 1, 2 or 3 and smooth_kappa >= 0, got %r" % (self,))
+        return self
+
+
 class Model3D(ModelBase):
     """Flow-3D/model/RIFE.py:18-275."""
     nd = 3
@@ -178,24 +200,46 @@ class Model3D(ModelBase):
             raise NotImplementedError("TTA is 'not implemented' in the reference too (RIFE.py:76)")
         return merged[2], flow, mask
 
-    def update(self, imgs, gt, learning_rate=0, mul=1, training=True, flow_gt=None, lap_loss=False):
+    def update(self, imgs, gt, learning_rate=0, mul=1, training=True, flow_gt=None, lap_loss=False, unsup=None):
         """`lap_loss=True` swaps the two L1 terms for the Laplacian-pyramid loss the reference has commented
         out (RIFE.py:126, 133: `(self.lap(merged[2], gt)).mean()`), computed by the 3-D pyramid kernels; the
-        default is the reference's active path."""
+        default is the reference's active path.  `unsup`: an `UnsupLoss` -- the photometric, census and smoothness
+        terms the reference's update holds commented out (RIFE.py:147-245) join loss_G with its weights, and the
+        returned dict gains 'loss_photo', 'loss_census', 'loss_smooth' (unweighted; 0 for a term that is off)."""
         # forward, backward and the optimiser step see ONE set of weights: their re-laid-out slabs are built by one
         # launch at the first convolution and dropped when the step ends (ops.prepared_weights)
         with ops.prepared_weights():
-            return self._update(imgs, gt, learning_rate, training, lap_loss)
+            return self._update(imgs, gt, learning_rate, training, lap_loss, unsup)
 
-    def _update(self, imgs, gt, learning_rate, training, lap_loss):
+    def _unsup_terms(self, unsup, pair, flow, gt):
+        """(loss_photo, loss_census, loss_smooth) of `unsup` on the last student block's warped pair, the final flow and
+        the (cropped) middle frame."""
+        zero = gt.new_zeros(())
+        w0, w1 = (t[(slice(None), slice(None)) + tuple(slice(0, s) for s in gt.shape[2:])] for t in pair)
+        photo = census = smooth = zero
+        if unsup.photo:
+            photo = 0.5 * (ops.robust_loss(w0, gt, None, ops.PEN_CHARBONNIER, unsup.charb_q, unsup.charb_eps ** 2) +
+                           ops.robust_loss(w1, gt, None, ops.PEN_CHARBONNIER, unsup.charb_q, unsup.charb_eps ** 2))
+        if unsup.census:
+            census = 0.5 * (ops.census3d_loss(w0, gt, unsup.census_radius, unsup.census_q) +
+                            ops.census3d_loss(w1, gt, unsup.census_radius, unsup.census_q))
+        if unsup.smooth:
+            smooth = ops.flow_smooth3d(flow, gt if unsup.smooth_kappa else None, unsup.charb_q, unsup.charb_eps,
+                                       unsup.smooth_kappa)
+        return photo, census, smooth
+
+    def _update(self, imgs, gt, learning_rate, training, lap_loss, unsup=None):
         self._set_lr(learning_rate)
         if training:
             self.train()
         else:
             self.eval()
         gt = gt.contiguous()  # (a channel slice of the loader's [B,3,...] batch: one copy here, none in the consumers)
+        net = self.flownet.module if isinstance(self.flownet, DDP) else self.flownet
+        net.keep_warped_pair = unsup is not None
         flow, mask, merged, flow_teacher, merged_teacher, loss_distill = self.flownet(
             (imgs, gt), scale=[4, 2, 1])
+        pair, net.warped_pair, net.keep_warped_pair = net.warped_pair, None, False
         sp = tuple(min(a, b) for a, b in zip(imgs.shape[2:], mask.shape[2:]))
         gt = gt[(slice(None), slice(None)) + tuple(slice(0, s) for s in sp)]
         pair_loss = self.lap if lap_loss else ops.l1_loss
@@ -204,6 +248,11 @@ class Model3D(ModelBase):
         # RIFE.py:141-143 also sums an L1 norm of all parameters that never reaches loss_G
         # (lambda_reg = 0 and the term is commented out of :158); it is not computed here.
         loss_G = loss_l1 * 1 + loss_tea * 1 + loss_distill * 0.1  # RIFE.py:151-158
+        extra = {}
+        if unsup is not None:
+            photo, census, smooth = self._unsup_terms(unsup, pair, flow[2], gt.contiguous())
+            loss_G = loss_G + photo * unsup.photo + census * unsup.census + smooth * unsup.smooth
+            extra = {'loss_photo': photo, 'loss_census': census, 'loss_smooth': smooth}
         if training:
             self.optimG.zero_grad()
             loss_G.backward()
@@ -214,7 +263,7 @@ class Model3D(ModelBase):
         return merged[2], {
             'merged_tea': merged_teacher, 'mask': mask, 'mask_tea': mask, 'flow': flow[2],
             'flow_tea': flow_teacher, 'loss_l1': loss_l1, 'loss_tea': loss_tea,
-            'loss_distill': loss_distill, 'loss_G': loss_G,
+            'loss_distill': loss_distill, 'loss_G': loss_G, **extra,
         }
 
 

@@ -210,24 +210,45 @@ def psnr01(pred, gt):
     return -10 * math.log10(max(float(torch.mean((gt - pred) * (gt - pred))), 1e-20))
 
 
-def evaluate(model, val_data, nd, dataset, device):
-    """Per-epoch validation: loss means and PSNR of student / teacher (train.py `evaluate`)."""
-    losses, psnr, psnr_tea = [], [], []
+_UNSUP_KEYS = ("loss_photo", "loss_census", "loss_smooth")
+
+
+def unsup_from_args(args, nd):
+    """The `UnsupLoss` of --photo / --census / --smooth (Flow-3D only), or None when all three are 0."""
+    if nd != 3 or not (args.photo or args.census or args.smooth):
+        return None
+    from .rife import UnsupLoss
+    return UnsupLoss(photo=args.photo, census=args.census, smooth=args.smooth, census_radius=args.census_radius,
+                     smooth_kappa=args.smooth_kappa)
+
+
+def unsup_text(terms=None):
+    """' photo:… census:… smooth:…' for a log line; '' when the terms are off."""
+    return "".join(" %s:%.4e" % (k[5:], float(v)) for k, v in zip(_UNSUP_KEYS, terms)) if terms else ""
+
+
+def evaluate(model, val_data, nd, dataset, device, unsup=None):
+    """Per-epoch validation: loss means and PSNR of student / teacher (train.py `evaluate`); with `unsup` a fourth
+    value, the means of the three unsupervised terms."""
+    losses, psnr, psnr_tea, terms = [], [], [], []
     for data in val_data:
         data = data.to(device, non_blocking=True)
         imgs, gt = data[:, :2], data[:, 2:3]
         with torch.no_grad():
             if nd == 3:
-                pred, info = model.update(imgs, gt, training=False)
+                pred, info = model.update(imgs, gt, training=False, **({} if unsup is None else {"unsup": unsup}))
             else:
                 pred, info = model.update(imgs, gt, dataset, training=False)
         losses.append(float(info['loss_G']))
+        if unsup is not None:
+            terms.append([float(info[k]) for k in _UNSUP_KEYS])
         sp = tuple(min(a, b) for a, b in zip(gt.shape[2:], pred.shape[2:]))
         cut = (slice(None), slice(None)) + tuple(slice(0, s) for s in sp)
         for j in range(gt.shape[0]):
             psnr.append(psnr01(pred[cut][j], gt[cut][j]))
             psnr_tea.append(psnr01(info['merged_tea'][cut][j], gt[cut][j]))
-    return float(np.mean(losses)), float(np.mean(psnr)), float(np.mean(psnr_tea))
+    out = float(np.mean(losses)), float(np.mean(psnr)), float(np.mean(psnr_tea))
+    return out if unsup is None else out + (np.mean(terms, axis=0).tolist(),)
 
 
 def run(args, Model, nd):
@@ -300,10 +321,12 @@ def run(args, Model, nd):
         if rank == 0:
             print("no weights found, training from scratch")
 
+    unsup = unsup_from_args(args, nd)
+    step_kwargs = {"dataset": args.dataset} if nd == 2 else {} if unsup is None else {"unsup": unsup}
     if args.mode != "train":
-        loss, p, pt = evaluate(model, val_data, nd, args.dataset, device)
+        loss, p, pt, *terms = evaluate(model, val_data, nd, args.dataset, device, unsup)
         if rank == 0:
-            print("test: loss_G %.4e  PSNR %.2f dB  (teacher %.2f dB)" % (loss, p, pt))
+            print("test: loss_G %.4e  PSNR %.2f dB  (teacher %.2f dB)%s" % (loss, p, pt, unsup_text(*terms)))
         if distributed:
             dist.destroy_process_group()
         return
@@ -327,15 +350,16 @@ def run(args, Model, nd):
             lr = get_learning_rate(step, max(total, 2001)) * world / 4  # train.py:167
             if use_graph:
                 if graph_step is None:
-                    graph_step = model.graphed_update(imgs, gt, **({} if nd == 3 else {"dataset": args.dataset}))
+                    graph_step = model.graphed_update(imgs, gt, **step_kwargs)
                 pred, info = graph_step(imgs, gt, lr)
             elif nd == 3:
-                pred, info = model.update(imgs, gt, lr, training=True)
+                pred, info = model.update(imgs, gt, lr, training=True, **step_kwargs)
             else:
                 pred, info = model.update(imgs, gt, args.dataset, lr, training=True)
             if rank == 0 and (i % args.log_every == 0):
                 print('epoch:{}/{} {}/{} time:{:.2f} loss_G:{:.4e}'.format(
-                    epoch, args.epoch, i, steps_per_epoch, time.time() - t0, float(info['loss_G'].detach())))
+                    epoch, args.epoch, i, steps_per_epoch, time.time() - t0, float(info['loss_G'].detach())) +
+                    unsup_text([info[k].detach() for k in _UNSUP_KEYS] if unsup is not None else None))
                 t0 = time.time()
             step += 1
         torch.cuda.synchronize(device)
@@ -344,9 +368,9 @@ def run(args, Model, nd):
             print("epoch %d train loop: %d steps in %.2f s = %.1f ms/step = %.2f pairs/s per rank (%s data, %s)" % (
                 epoch, steps_per_epoch, dt, dt / steps_per_epoch * 1e3, steps_per_epoch * args.batch_size / dt,
                 "host" if args.host_data else "device-resident series" if from_file else "device-generated", "hip-graph replay" if use_graph else "eager launches"))
-        loss, p, pt = evaluate(model, val_data, nd, args.dataset, device)
+        loss, p, pt, *terms = evaluate(model, val_data, nd, args.dataset, device, unsup)
         if rank == 0:
-            print("eval epoch %d: loss_G %.4e  PSNR %.2f dB  (teacher %.2f dB)" % (epoch, loss, p, pt))
+            print("eval epoch %d: loss_G %.4e  PSNR %.2f dB  (teacher %.2f dB)%s" % (epoch, loss, p, pt, unsup_text(*terms)))
             if nd == 2 or best is None or loss <= best:  # 2-D saves every epoch, 3-D on improvement
                 best = loss if best is None else min(best, loss)
                 model.save_model(model_name, log_path, 0)
@@ -393,6 +417,18 @@ def add_common_args(parser, nd):
                         help='map the stored values to [0,1] by the range of the file / of each triplet, or leave them')
     parser.add_argument('--eager', action='store_true',
                         help='N = 1: eager launches per step instead of replaying the step from one HIP graph')
+    if nd == 3:
+        # the flow-side unsupervised terms (rife.UnsupLoss); all off by default
+        parser.add_argument('--photo', type=float, default=0., metavar='W',
+                            help='weight of the Charbonnier term of each warped frame against the middle frame')
+        parser.add_argument('--census', type=float, default=0., metavar='W',
+                            help='weight of the 3-D census term of the same two pairs')
+        parser.add_argument('--smooth', type=float, default=0., metavar='W',
+                            help='weight of the first-order smoothness of the flow')
+        parser.add_argument('--census_radius', type=int, choices=(1, 2, 3), default=1,
+                            help='census patch (2 r + 1)^3; the cost grows with its cube')
+        parser.add_argument('--smooth_kappa', type=float, default=0., metavar='K',
+                            help='edge-aware smoothness: weight exp(-K |difference of the middle frame|)')
     parser.add_argument('--log_every', type=int, default=10)
     parser.add_argument('--log_path', default='train_log')
     parser.add_argument('--model_name', default='flownet.pkl')
