@@ -144,7 +144,11 @@ int fs_upsample_warp3d_pair_bwd3(const float* img0, const float* img1, const flo
  *                            C == 1, W_in % 4 == 0, the 37-plane x 72-column window fits the sampled volume, 16-byte
  *                            aligned tensors, flow gradient only)
  * `backward` != 0: fs_warp3d*_bwd* with `with_grad_in` saying whether grad_in / grad_img* are asked for; a negative
- * return value is -FS_ERR_*.  (bench.py names the kernel symbol of its roofline records with it.) */
+ * return value is -FS_ERR_*.  (bench.py names the kernel symbol of its roofline records with it.)
+ * The query sees in0, in1 and flow only.  A raw-ABI call whose out / grad_out / grad_flow / addend is not 16-byte
+ * aligned, or whose addend / grad_out batch stride is not a multiple of 4 floats, runs the scalar gather kernels even
+ * where the query answers FS_W3_KERNEL_RC (tests/mem_ledger.py, rows with plan None); the binding never makes such a
+ * call: it allocates those tensors, and its slices are channel slices of W % 4 == 0 tensors. */
 enum { FS_W3_KERNEL_GATHER = 0, FS_W3_KERNEL_RC = 1 };
 int fs_warp3d_kernel_id(const float* in0, const float* in1, const float* flow, int B, int C, const int* in_dhw,
                         int D, int H, int W, int backward, int with_grad_in);

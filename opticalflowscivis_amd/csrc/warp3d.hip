@@ -361,10 +361,14 @@ struct Mover {
   }
 };
 
-// (UPS: two 512-thread workgroups per CU = 4 waves per SIMD, i.e. <= 128 VGPRs, like the plain kernel)
+// (two 512-thread workgroups per CU = 4 waves per SIMD, i.e. <= 128 VGPRs)
+// UPS is always true: the plain forward warp left this kernel for warp3d_fwd_ring_kernel / warp3d_rc_kernel and its
+// branches here were deleted; the parameter stays because the symbol `warp3d_fwd_kernel<512, *, true>` is the key of the
+// recorded profiles (profiles/).
 template <int NT, bool VEC, bool UPS>
-__global__ __launch_bounds__(NT, UPS ? 4 : 1) void warp3d_fwd_kernel(W3Fwd io, const float* __restrict__ flow, UpP u,
+__global__ __launch_bounds__(NT, 4) void warp3d_fwd_kernel(W3Fwd io, const float* __restrict__ flow, UpP u,
                                                         W3P p) {
+  static_assert(UPS, "the fused up-sampling form is the only one left");
   using M = Mover<NT, VEC>;
   constexpr int NW = TW / (NT / 64);  // voxels per thread and slice in the h-major phase
   const float* __restrict__ in = io.in[blockIdx.y];
@@ -378,7 +382,7 @@ __global__ __launch_bounds__(NT, UPS ? 4 : 1) void warp3d_fwd_kernel(W3Fwd io, c
   const size_t vol = (size_t)p.D * HW;
   const size_t ivol = (size_t)p.Di * p.Hi * p.Wi;
   const size_t fch = (size_t)b * p.flowC + 3 * blockIdx.y;  // first flow channel of this pair member
-  const float* fb = UPS ? nullptr : flow + fch * vol;
+  (void)flow;
   const int dEnd = min(d0 + p.dc, p.D);
 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -386,37 +390,32 @@ __global__ __launch_bounds__(NT, UPS ? 4 : 1) void warp3d_fwd_kernel(W3Fwd io, c
   const float lin_h = fs::linspace_pm1(h, p.H, p.stepH);
 
   typename M::elem r0[M::PASSES], r1[M::PASSES], r2[M::PASSES];
-  typename M::elem q0[M::PASSES], q1[M::PASSES], q2[M::PASSES];  // UPS: the running flow's tile (dead otherwise)
-  __shared__ typename M::Brick sS[UPS ? 3 : 1];
-  if constexpr (UPS) {
+  typename M::elem q0[M::PASSES], q1[M::PASSES], q2[M::PASSES];  // the running flow's tile
+  __shared__ typename M::Brick sS[3];
+  {
     const size_t svol = (size_t)u.Ds * u.Hs * u.Ws;
     M::up_stage(sS, u.small + fch * svol, svol, p, u, d0, h0, w0);
     __syncthreads();
   }
-  // the three flow planes of slice d: loads issued here -- of the flow itself (plain warp) or of the running
-  // flow (UPS; blended with the up-sampled delta by up_tiles at the top of the slice's iteration)
+  // the three planes of the running flow of slice d: loads issued here, blended with the up-sampled delta by up_tiles
+  // at the top of the slice's iteration
   auto flow_tiles = [&](int d) {
-    if constexpr (UPS) {
-      if (u.prev != nullptr) {
-        const float* pp = u.prev + fch * vol + (size_t)d * HW;
-        M::up_prefetch(pp, p, h0, w0, q0); M::up_prefetch(pp + vol, p, h0, w0, q1);
-        M::up_prefetch(pp + 2 * vol, p, h0, w0, q2);
-      }
-    } else {
-      const float* f = fb + (size_t)d * HW;
-      M::load(f, p, h0, w0, r0); M::load(f + vol, p, h0, w0, r1); M::load(f + 2 * vol, p, h0, w0, r2);
+    if (u.prev != nullptr) {
+      const float* pp = u.prev + fch * vol + (size_t)d * HW;
+      M::up_prefetch(pp, p, h0, w0, q0); M::up_prefetch(pp + vol, p, h0, w0, q1);
+      M::up_prefetch(pp + 2 * vol, p, h0, w0, q2);
     }
   };
   auto up_tiles = [&](int d) {
     float* op = u.fout + fch * vol + (size_t)d * HW;
     const bool hp = u.prev != nullptr;
     M::up_finish(sS[0], hp, op, p, u, d0, d, h0, w0, q0, r0);
-    M::up_finish(sS[UPS ? 1 : 0], hp, op + vol, p, u, d0, d, h0, w0, q1, r1);
-    M::up_finish(sS[UPS ? 2 : 0], hp, op + 2 * vol, p, u, d0, d, h0, w0, q2, r2);
+    M::up_finish(sS[1], hp, op + vol, p, u, d0, d, h0, w0, q1, r1);
+    M::up_finish(sS[2], hp, op + 2 * vol, p, u, d0, d, h0, w0, q2, r2);
   };
   flow_tiles(d0);
   for (int d = d0; d < dEnd; ++d) {
-    if constexpr (UPS) up_tiles(d);  // blend the loaded corners, write the accumulated flow, fill r0..r2
+    up_tiles(d);  // blend the loaded corners, write the accumulated flow, fill r0..r2
     // phase 1: flow tile of this slice (already in registers) -> LDS
     M::to_lds(sF[0], r0); M::to_lds(sF[1], r1); M::to_lds(sF[2], r2);
     __syncthreads();
