@@ -884,94 +884,109 @@ bool vec_ok(const W3P& p, const void* a, const void* b, const void* c, const voi
   return (p.W % 4 == 0) && al(a) && al(b) && al(c) && al(d);
 }
 
-int launch_fwd(const W3Fwd& io, int npair, const float* flow, const UpP* up, W3P& p, fs_stream_t stream) {
-  p.flowC = 3 * npair;
-  hipStream_t st = (hipStream_t)stream;
+// The one place a call's kernel is decided: launch_fwd / launch_bwd run what these return, fs_warp3d_kernel_id reports it.
+enum class W3K { RC, RING_VEC, RING_SCALAR, UPS_VEC, UPS_SCALAR, BWD_VEC, BWD_SCALAR };
+struct W3Pick { W3K kernel; int dc; };  // dc: d-slices per workgroup the kernel runs with
+
+int rc_mode() { static const int m = (int)FS_AB_ENV_LL("FLOWSCI_W3_RC", 1); return m; }  // ablation build: 0 = round-4 kernels, 11.. = DBG forms
+
+W3Pick pick_fwd(const W3P& p, const W3Fwd& io, int npair, const float* flow, const UpP* up) {
   if (up != nullptr) {
-    const bool vec = vec_ok(p, up->prev, up->fout, io.out[0], io.out[1]);
     // 4 x factor slices per workgroup: the low-resolution brick (staged once per workgroup) then carries 4 source slices + 2
     // of halo instead of 2 + 2 -- its re-reads were the 1.26x HBM traffic of round 3 (profiles/r03_pmc_traffic.json)
-    p.dc = (int)FS_AB_ENV_LL("FLOWSCI_W3_UPS_DC", 4 * (up->rs < 0.3f ? 4 : 2));
-    p.nDC = fs::cdiv(p.D, p.dc);
-    const dim3 g((unsigned)((long long)p.B * p.nDC * p.tilesH * p.tilesW), npair);
-    if (vec) hipLaunchKernelGGL((warp3d_fwd_kernel<512, true, true>), g, dim3(512), 0, st, io, flow, *up, p);
-    else hipLaunchKernelGGL((warp3d_fwd_kernel<512, false, true>), g, dim3(512), 0, st, io, flow, *up, p);
-  } else {
-    const bool vec = vec_ok(p, flow, io.out[0], io.out[1], nullptr);
-    // round 5: ring pipeline with the gather source in an LDS row cache (warp3d_rc.hpp) wherever its window fits the volume
-    static const int rc_mode = (int)FS_AB_ENV_LL("FLOWSCI_W3_RC", 1);  // ablation build: 0 = round-4 kernels, 11.. = DBG forms
-    if (vec && rc_mode != 0 && rc::applicable(p, io.in[0], io.in[1])) {
-      p.dc = (int)FS_AB_ENV_LL("FLOWSCI_W3_RC_DC", rc::pick_dc(p, npair));
-      p.nDC = fs::cdiv(p.D, p.dc);
-      const dim3 gc((unsigned)((long long)p.B * p.nDC * p.tilesH * p.tilesW), npair);
-      const dim3 bc(64 * (NCW + 2));
+    const int dc = (int)FS_AB_ENV_LL("FLOWSCI_W3_UPS_DC", 4 * (up->rs < 0.3f ? 4 : 2));
+    return {vec_ok(p, up->prev, up->fout, io.out[0], io.out[1]) ? W3K::UPS_VEC : W3K::UPS_SCALAR, dc};
+  }
+  const bool vec = vec_ok(p, flow, io.out[0], io.out[1], nullptr);
+  // round 5: ring pipeline with the gather source in an LDS row cache (warp3d_rc.hpp) wherever its window fits the volume
+  if (vec && rc_mode() != 0 && rc::applicable(p, io.in[0], io.in[1]))
+    return {W3K::RC, (int)FS_AB_ENV_LL("FLOWSCI_W3_RC_DC", rc::pick_dc(p, npair))};
+  // the ring kernel walks 16 slices per workgroup (one workgroup per CU; 2 048 workgroups at 2 x 256^3)
+  return {vec ? W3K::RING_VEC : W3K::RING_SCALAR, (int)FS_AB_ENV_LL("FLOWSCI_W3_RING_DC", 16)};
+}
+
+W3Pick pick_bwd(const W3P& p, const W3Bwd& io, int npair, bool with_gin, const float* flow, const float* gflow,
+                const W3Add& gadd) {
+  const bool vec = vec_ok(p, flow, gflow, io.gout[0], io.gout[1]) && vec_ok(p, gadd.a[0], gadd.a[1], gadd.a[2], nullptr) &&
+                   gadd.bs[0] % 4 == 0 && gadd.bs[1] % 4 == 0 && gadd.bs[2] % 4 == 0 && io.gbs[0] % 4 == 0 && io.gbs[1] % 4 == 0;
+  if (vec && rc_mode() != 0 && !with_gin && gflow != nullptr && rc::applicable(p, io.in[0], io.in[1]))
+    return {W3K::RC, (int)FS_AB_ENV_LL("FLOWSCI_W3_RC_DC", rc::pick_dc(p, npair))};
+  return {vec ? W3K::BWD_VEC : W3K::BWD_SCALAR, p.dc};
+}
+
+// the launch geometry every kernel shares: one workgroup per (batch, d-chunk, h-tile, w-tile), blockIdx.y = member of the pair
+dim3 set_chunks(W3P& p, const W3Pick& k, int npair) {
+  p.flowC = 3 * npair;
+  p.dc = k.dc;
+  p.nDC = fs::cdiv(p.D, p.dc);
+  return dim3((unsigned)((long long)p.B * p.nDC * p.tilesH * p.tilesW), npair);
+}
+
+template <bool BWD, int NMW_, int R>
+void launch_rc(const dim3& g, hipStream_t st, const W3Fwd& fio, const W3Bwd& bio, const float* flow, float* gflow,
+               const W3Add& gadd, const W3P& p) {
+  const dim3 bc(64 * (NCW + NMW_));
 #ifdef FS_ABLATION
-      if (rc_mode == 11) { hipLaunchKernelGGL((rc::warp3d_rc_kernel<false, 2, 6, 1>), gc, bc, 0, st, io, W3Bwd{}, flow, nullptr, W3Add{}, p); FS_LAUNCH_CHECK(); return FS_OK; }
-      if (rc_mode == 12) { hipLaunchKernelGGL((rc::warp3d_rc_kernel<false, 2, 6, 2>), gc, bc, 0, st, io, W3Bwd{}, flow, nullptr, W3Add{}, p); FS_LAUNCH_CHECK(); return FS_OK; }
-      if (rc_mode == 13) { hipLaunchKernelGGL((rc::warp3d_rc_kernel<false, 2, 6, 3>), gc, bc, 0, st, io, W3Bwd{}, flow, nullptr, W3Add{}, p); FS_LAUNCH_CHECK(); return FS_OK; }
+#define W3_RC_DBG(N) \
+  if (rc_mode() == 10 + N) { hipLaunchKernelGGL((rc::warp3d_rc_kernel<BWD, NMW_, R, N>), g, bc, 0, st, fio, bio, flow, gflow, gadd, p); return; }
+  W3_RC_DBG(1) W3_RC_DBG(2) W3_RC_DBG(3)
 #endif
-      hipLaunchKernelGGL((rc::warp3d_rc_kernel<false, 2, 6>), gc, bc, 0, st, io, W3Bwd{}, flow, nullptr, W3Add{}, p);
-      FS_LAUNCH_CHECK();
-      return FS_OK;
+  hipLaunchKernelGGL((rc::warp3d_rc_kernel<BWD, NMW_, R>), g, bc, 0, st, fio, bio, flow, gflow, gadd, p);
+}
+
+int launch_fwd(const W3Fwd& io, int npair, const float* flow, const UpP* up, W3P& p, fs_stream_t stream) {
+  const W3Pick k = pick_fwd(p, io, npair, flow, up);
+  const dim3 g = set_chunks(p, k, npair);
+  hipStream_t st = (hipStream_t)stream;
+  switch (k.kernel) {
+    case W3K::UPS_VEC: hipLaunchKernelGGL((warp3d_fwd_kernel<512, true, true>), g, dim3(512), 0, st, io, flow, *up, p); break;
+    case W3K::UPS_SCALAR: hipLaunchKernelGGL((warp3d_fwd_kernel<512, false, true>), g, dim3(512), 0, st, io, flow, *up, p); break;
+    case W3K::RC: launch_rc<false, 2, 6>(g, st, io, W3Bwd{}, flow, nullptr, W3Add{}, p); break;
+    case W3K::RING_VEC: {
+#ifdef FS_ABLATION
+      static const int ring = (int)FS_AB_ENV_LL("FLOWSCI_W3_RING", 0);  // 3..5: that many flow stages; +10: non-temporal DMA
+#define W3_RING_CASE(R, A, DBG, ID) \
+      if (ring == ID) { hipLaunchKernelGGL((warp3d_fwd_ring_kernel<true, A, R, DBG>), g, dim3(NT2), 0, st, io, flow, p); break; }
+      W3_RING_CASE(3, 0, 0, 3) W3_RING_CASE(4, 0, 0, 4) W3_RING_CASE(5, 0, 0, 5) W3_RING_CASE(3, 2, 0, 13) W3_RING_CASE(5, 2, 0, 15)
+      W3_RING_CASE(4, 2, 1, 101) W3_RING_CASE(4, 2, 2, 102) W3_RING_CASE(4, 2, 3, 103) W3_RING_CASE(4, 2, 4, 104) W3_RING_CASE(4, 2, 5, 105)
+#endif
+      hipLaunchKernelGGL((warp3d_fwd_ring_kernel<true, 2, 4>), g, dim3(NT2), 0, st, io, flow, p);
+      break;
     }
-    // the ring kernel walks 16 slices per workgroup (one workgroup per CU; 2 048 workgroups at 2 x 256^3)
-    p.dc = (int)FS_AB_ENV_LL("FLOWSCI_W3_RING_DC", 16);
-    p.nDC = fs::cdiv(p.D, p.dc);
-    const dim3 gr((unsigned)((long long)p.B * p.nDC * p.tilesH * p.tilesW), npair);
-#ifdef FS_ABLATION
-    static const int ring = (int)FS_AB_ENV_LL("FLOWSCI_W3_RING", 0);  // 3..5: that many flow stages; +10: non-temporal DMA
-#define W3_RING_CASE(R, A) \
-    if (vec && ring == R + (A ? 10 : 0)) { hipLaunchKernelGGL((warp3d_fwd_ring_kernel<true, A, R>), gr, dim3(NT2), 0, st, io, flow, p); FS_LAUNCH_CHECK(); return FS_OK; }
-    W3_RING_CASE(3, 0) W3_RING_CASE(4, 0) W3_RING_CASE(5, 0) W3_RING_CASE(3, 2) W3_RING_CASE(5, 2)
-    if (vec && ring == 101) { hipLaunchKernelGGL((warp3d_fwd_ring_kernel<true, 2, 4, 1>), gr, dim3(NT2), 0, st, io, flow, p); FS_LAUNCH_CHECK(); return FS_OK; }
-    if (vec && ring == 103) { hipLaunchKernelGGL((warp3d_fwd_ring_kernel<true, 2, 4, 3>), gr, dim3(NT2), 0, st, io, flow, p); FS_LAUNCH_CHECK(); return FS_OK; }
-    if (vec && ring == 104) { hipLaunchKernelGGL((warp3d_fwd_ring_kernel<true, 2, 4, 4>), gr, dim3(NT2), 0, st, io, flow, p); FS_LAUNCH_CHECK(); return FS_OK; }
-    if (vec && ring == 105) { hipLaunchKernelGGL((warp3d_fwd_ring_kernel<true, 2, 4, 5>), gr, dim3(NT2), 0, st, io, flow, p); FS_LAUNCH_CHECK(); return FS_OK; }
-    if (vec && ring == 102) { hipLaunchKernelGGL((warp3d_fwd_ring_kernel<true, 2, 4, 2>), gr, dim3(NT2), 0, st, io, flow, p); FS_LAUNCH_CHECK(); return FS_OK; }
-#endif
-    if (vec) hipLaunchKernelGGL((warp3d_fwd_ring_kernel<true, 2, 4>), gr, dim3(NT2), 0, st, io, flow, p);
-    else hipLaunchKernelGGL((warp3d_fwd_ring_kernel<false, 0, 3>), gr, dim3(NT2), 0, st, io, flow, p);
+    case W3K::RING_SCALAR: hipLaunchKernelGGL((warp3d_fwd_ring_kernel<false, 0, 3>), g, dim3(NT2), 0, st, io, flow, p); break;
+    default: return FS_ERR_ARG;  // pick_fwd gives no backward kernel
   }
   FS_LAUNCH_CHECK();
   return FS_OK;
-}
-
-template <int NT, bool VEC>
-void launch_bwd_t(const W3Bwd& io, const dim3& g, bool with_gin, const float* flow, float* gflow,
-                  const W3Add& gadd, const W3P& p, hipStream_t st) {
-  if (with_gin)
-    hipLaunchKernelGGL((warp3d_bwd_kernel<NT, VEC, true>), g, dim3(NT), 0, st, io, flow, gflow, gadd, p);
-  else
-    hipLaunchKernelGGL((warp3d_bwd_kernel<NT, VEC, false>), g, dim3(NT), 0, st, io, flow, gflow, gadd, p);
 }
 
 int launch_bwd(const W3Bwd& io, int npair, bool with_gin, const float* flow, float* gflow, const W3Add& gadd,
                W3P& p, fs_stream_t stream) {
-  const unsigned grid = (unsigned)((long long)p.B * p.nDC * p.tilesH * p.tilesW);
-  p.flowC = 3 * npair;
+  const W3Pick k = pick_bwd(p, io, npair, with_gin, flow, gflow, gadd);
+  const dim3 g = set_chunks(p, k, npair);
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = vec_ok(p, flow, gflow, io.gout[0], io.gout[1]) && vec_ok(p, gadd.a[0], gadd.a[1], gadd.a[2], nullptr) &&
-                   gadd.bs[0] % 4 == 0 && gadd.bs[1] % 4 == 0 && gadd.bs[2] % 4 == 0 && io.gbs[0] % 4 == 0 && io.gbs[1] % 4 == 0;
-  static const int rc_mode = (int)FS_AB_ENV_LL("FLOWSCI_W3_RC", 1);
-  if (vec && rc_mode != 0 && !with_gin && gflow != nullptr && rc::applicable(p, io.in[0], io.in[1])) {
-    p.dc = (int)FS_AB_ENV_LL("FLOWSCI_W3_RC_DC", rc::pick_dc(p, npair));
-    p.nDC = fs::cdiv(p.D, p.dc);
-    const dim3 gc((unsigned)((long long)p.B * p.nDC * p.tilesH * p.tilesW), npair);
-    const dim3 bc(64 * (NCW + 4));
-#ifdef FS_ABLATION
-    if (rc_mode == 11) { hipLaunchKernelGGL((rc::warp3d_rc_kernel<true, 4, 5, 1>), gc, bc, 0, st, W3Fwd{}, io, flow, gflow, gadd, p); FS_LAUNCH_CHECK(); return FS_OK; }
-    if (rc_mode == 12) { hipLaunchKernelGGL((rc::warp3d_rc_kernel<true, 4, 5, 2>), gc, bc, 0, st, W3Fwd{}, io, flow, gflow, gadd, p); FS_LAUNCH_CHECK(); return FS_OK; }
-    if (rc_mode == 13) { hipLaunchKernelGGL((rc::warp3d_rc_kernel<true, 4, 5, 3>), gc, bc, 0, st, W3Fwd{}, io, flow, gflow, gadd, p); FS_LAUNCH_CHECK(); return FS_OK; }
-#endif
-    hipLaunchKernelGGL((rc::warp3d_rc_kernel<true, 4, 5>), gc, bc, 0, st, W3Fwd{}, io, flow, gflow, gadd, p);
-    FS_LAUNCH_CHECK();
-    return FS_OK;
+  switch (k.kernel) {
+    case W3K::RC: launch_rc<true, 4, 5>(g, st, W3Fwd{}, io, flow, gflow, gadd, p); break;
+    case W3K::BWD_VEC:
+      if (with_gin) hipLaunchKernelGGL((warp3d_bwd_kernel<256, true, true>), g, dim3(256), 0, st, io, flow, gflow, gadd, p);
+      else hipLaunchKernelGGL((warp3d_bwd_kernel<256, true, false>), g, dim3(256), 0, st, io, flow, gflow, gadd, p);
+      break;
+    case W3K::BWD_SCALAR:
+      if (with_gin) hipLaunchKernelGGL((warp3d_bwd_kernel<256, false, true>), g, dim3(256), 0, st, io, flow, gflow, gadd, p);
+      else hipLaunchKernelGGL((warp3d_bwd_kernel<256, false, false>), g, dim3(256), 0, st, io, flow, gflow, gadd, p);
+      break;
+    default: return FS_ERR_ARG;  // pick_bwd gives no forward kernel
   }
-  const dim3 g(grid, npair);
-  if (vec) launch_bwd_t<256, true>(io, g, with_gin, flow, gflow, gadd, p, st);
-  else launch_bwd_t<256, false>(io, g, with_gin, flow, gflow, gadd, p, st);
   FS_LAUNCH_CHECK();
   return FS_OK;
+}
+
+// the factor / extent / overflow checks of the fused "upsample -> warp" entry points, then the full-resolution parameters
+int make_params_up(W3P& p, int B, int C, const int* in_dhw, int Ds, int Hs, int Ws, int factor) {
+  if (factor != 2 && factor != 4) return FS_ERR_ARG;
+  if (Ds < 1 || Hs < 1 || Ws < 1) return FS_ERR_SHAPE;
+  if ((long long)Ds * Hs * Ws * factor * factor * factor >= (1ll << 31)) return FS_ERR_SHAPE;
+  return make_params(p, B, C, in_dhw, Ds * factor, Hs * factor, Ws * factor);
 }
 
 }  // namespace
@@ -981,8 +996,7 @@ extern "C" int fs_warp3d_fwd(const float* in, const float* flow, float* out, int
   FS_ENTER();
   FS_REQUIRE_PTR(in); FS_REQUIRE_PTR(flow); FS_REQUIRE_PTR(out);
   W3P p;
-  const int rc = make_params(p, B, C, in_dhw, D, H, W);
-  if (rc != FS_OK) return rc;
+  if (const int rc = make_params(p, B, C, in_dhw, D, H, W); rc != FS_OK) return rc;
   W3Fwd io = {{in, nullptr}, {out, nullptr}};
   return launch_fwd(io, 1, flow, nullptr, p, stream);
 }
@@ -994,8 +1008,7 @@ extern "C" int fs_warp3d_bwd(const float* in, const float* flow, const float* gr
   FS_REQUIRE_PTR(in); FS_REQUIRE_PTR(flow); FS_REQUIRE_PTR(grad_out);
   if (grad_in == nullptr && grad_flow == nullptr) return FS_ERR_NULLPTR;
   W3P p;
-  const int rc = make_params(p, B, C, in_dhw, D, H, W);
-  if (rc != FS_OK) return rc;
+  if (const int rc = make_params(p, B, C, in_dhw, D, H, W); rc != FS_OK) return rc;
   W3Bwd io = {{in, nullptr}, {grad_out, nullptr}, {grad_in, nullptr}};
   return launch_bwd(io, 1, grad_in != nullptr, flow, grad_flow, W3Add{}, p, stream);
 }
@@ -1007,8 +1020,7 @@ extern "C" int fs_warp3d_pair_fwd(const float* img0, const float* img1, const fl
   FS_REQUIRE_PTR(img0); FS_REQUIRE_PTR(img1); FS_REQUIRE_PTR(flow6);
   FS_REQUIRE_PTR(out0); FS_REQUIRE_PTR(out1);
   W3P p;
-  const int rc = make_params(p, B, C, in_dhw, D, H, W);
-  if (rc != FS_OK) return rc;
+  if (const int rc = make_params(p, B, C, in_dhw, D, H, W); rc != FS_OK) return rc;
   W3Fwd io = {{img0, img1}, {out0, out1}};
   return launch_fwd(io, 2, flow6, nullptr, p, stream);
 }
@@ -1023,8 +1035,7 @@ extern "C" int fs_warp3d_pair_bwd(const float* img0, const float* img1, const fl
   if ((grad_img0 == nullptr) != (grad_img1 == nullptr)) return FS_ERR_NULLPTR;  // both or neither
   if (grad_img0 == nullptr && grad_flow6 == nullptr) return FS_ERR_NULLPTR;
   W3P p;
-  const int rc = make_params(p, B, C, in_dhw, D, H, W);
-  if (rc != FS_OK) return rc;
+  if (const int rc = make_params(p, B, C, in_dhw, D, H, W); rc != FS_OK) return rc;
   W3Bwd io = {{img0, img1}, {grad_out0, grad_out1}, {grad_img0, grad_img1}};
   return launch_bwd(io, 2, grad_img0 != nullptr, flow6, grad_flow6, W3Add{}, p, stream);
 }
@@ -1043,8 +1054,7 @@ extern "C" int fs_warp3d_pair_bwd_acc(const float* img0, const float* img1, cons
   FS_REQUIRE_PTR(grad_out0); FS_REQUIRE_PTR(grad_out1); FS_REQUIRE_PTR(grad_flow6);
   if ((grad_img0 == nullptr) != (grad_img1 == nullptr)) return FS_ERR_NULLPTR;
   W3P p;
-  const int rc = make_params(p, B, C, in_dhw, D, H, W);
-  if (rc != FS_OK) return rc;
+  if (const int rc = make_params(p, B, C, in_dhw, D, H, W); rc != FS_OK) return rc;
   W3Bwd io = {{img0, img1}, {grad_out0, grad_out1}, {grad_img0, grad_img1}};
   const long long bs = (long long)6 * D * H * W;
   return launch_bwd(io, 2, grad_img0 != nullptr, flow6, grad_flow6, W3Add{{grad_flow_add, nullptr, nullptr}, {bs, 0, 0}}, p,
@@ -1068,8 +1078,7 @@ extern "C" int fs_warp3d_pair_bwd_acc3(const float* img0, const float* img1, con
   FS_REQUIRE_PTR(grad_out0); FS_REQUIRE_PTR(grad_out1); FS_REQUIRE_PTR(grad_flow6);
   if ((grad_img0 == nullptr) != (grad_img1 == nullptr)) return FS_ERR_NULLPTR;
   W3P p;
-  const int rc = make_params(p, B, C, in_dhw, D, H, W);
-  if (rc != FS_OK) return rc;
+  if (const int rc = make_params(p, B, C, in_dhw, D, H, W); rc != FS_OK) return rc;
   const long long fl = (long long)6 * D * H * W;
   if ((add0 && batch_stride0 < fl) || (add1 && batch_stride1 < fl) || (add2 && batch_stride2 < fl)) return FS_ERR_ARG;
   const long long gl = (long long)C * D * H * W;  // 0 = dense
@@ -1082,14 +1091,12 @@ extern "C" int fs_warp3d_pair_bwd_acc3(const float* img0, const float* img1, con
 extern "C" int fs_warp3d_kernel_id(const float* in0, const float* in1, const float* flow, int B, int C, const int* in_dhw,
                                    int D, int H, int W, int backward, int with_grad_in) {
   W3P p;
-  const int rc = make_params(p, B, C, in_dhw, D, H, W);
-  if (rc != FS_OK) return -rc;
-  // launch_fwd / launch_bwd's own conditions (the remaining operands of a call are 16-byte aligned whenever these are:
-  // the binding allocates them)
-  const bool vec = vec_ok(p, flow, nullptr, nullptr, nullptr);
-  static const int rc_mode = (int)FS_AB_ENV_LL("FLOWSCI_W3_RC", 1);
-  if (vec && rc_mode != 0 && !(backward && with_grad_in) && rc::applicable(p, in0, in1)) return FS_W3_KERNEL_RC;
-  return FS_W3_KERNEL_GATHER;
+  if (const int rc = make_params(p, B, C, in_dhw, D, H, W); rc != FS_OK) return -rc;
+  alignas(16) float al[4];  // stands for every operand the query is not given: 16-byte aligned (the binding allocates them)
+  const int npair = in1 != nullptr ? 2 : 1;
+  const W3Pick k = backward ? pick_bwd(p, W3Bwd{{in0, in1}, {al, al}, {}, {}}, npair, with_grad_in != 0, flow, al, W3Add{})
+                            : pick_fwd(p, W3Fwd{{in0, in1}, {al, al}}, npair, flow, nullptr);
+  return k.kernel == W3K::RC ? FS_W3_KERNEL_RC : FS_W3_KERNEL_GATHER;
 }
 
 // "upsample flow x scale -> warp" in one kernel.  flow_out = prev_flow + scale *
@@ -1102,12 +1109,8 @@ extern "C" int fs_upsample_warp3d_pair_fwd(const float* img0, const float* img1,
   FS_ENTER();
   FS_REQUIRE_PTR(img0); FS_REQUIRE_PTR(img1); FS_REQUIRE_PTR(delta); FS_REQUIRE_PTR(flow_out);
   FS_REQUIRE_PTR(out0); FS_REQUIRE_PTR(out1);
-  if (factor != 2 && factor != 4) return FS_ERR_ARG;
-  if (Ds < 1 || Hs < 1 || Ws < 1) return FS_ERR_SHAPE;
-  if ((long long)Ds * Hs * Ws * factor * factor * factor >= (1ll << 31)) return FS_ERR_SHAPE;
   W3P p;
-  const int rc = make_params(p, B, C, in_dhw, Ds * factor, Hs * factor, Ws * factor);
-  if (rc != FS_OK) return rc;
+  if (const int rc = make_params_up(p, B, C, in_dhw, Ds, Hs, Ws, factor); rc != FS_OK) return rc;
   UpP u = {delta, prev_flow, flow_out, Ds, Hs, Ws, 1.0f / (float)factor, scale};
   W3Fwd io = {{img0, img1}, {out0, out1}};
   return launch_fwd(io, 2, nullptr, &u, p, stream);
@@ -1128,16 +1131,13 @@ extern "C" int fs_upsample_warp3d_pair_bwd3(const float* img0, const float* img1
                                             float* grad_delta, float* ws, int B, int C, const int* in_dhw, int Ds,
                                             int Hs, int Ws, int factor, float scale, fs_stream_t stream) {
   FS_REQUIRE_PTR(grad_delta); FS_REQUIRE_PTR(ws);
-  if (factor != 2 && factor != 4) return FS_ERR_ARG;
-  if (Ds < 1 || Hs < 1 || Ws < 1) return FS_ERR_SHAPE;
-  if ((long long)Ds * Hs * Ws * factor * factor * factor >= (1ll << 31)) return FS_ERR_SHAPE;
-  const int D = Ds * factor, H = Hs * factor, W = Ws * factor;
-  int rc = fs_warp3d_pair_bwd_acc3(img0, img1, flow6, grad_out0, gout_batch_stride0, grad_out1, gout_batch_stride1,
-                                   nullptr, nullptr, add0, batch_stride0, add1,
-                                   batch_stride1, add2, batch_stride2, grad_flow_total, B, C, in_dhw, D, H, W, stream);
+  W3P p;
+  if (const int rc = make_params_up(p, B, C, in_dhw, Ds, Hs, Ws, factor); rc != FS_OK) return rc;
+  const int rc = fs_warp3d_pair_bwd_acc3(img0, img1, flow6, grad_out0, gout_batch_stride0, grad_out1, gout_batch_stride1, nullptr,
+                                         nullptr, add0, batch_stride0, add1, batch_stride1, add2, batch_stride2, grad_flow_total, B,
+                                         C, in_dhw, p.D, p.H, p.W, stream);
   if (rc != FS_OK) return rc;
-  return fs_interp3d_bwd_scaled(grad_flow_total, grad_delta, ws, B, 6, Ds, Hs, Ws, D, H, W, factor, 1, scale,
-                                stream);
+  return fs_interp3d_bwd_scaled(grad_flow_total, grad_delta, ws, B, 6, Ds, Hs, Ws, p.D, p.H, p.W, factor, 1, scale, stream);
 }
 
 extern "C" int fs_upsample_warp3d_pair_bwd(const float* img0, const float* img1, const float* flow6,
@@ -1146,13 +1146,10 @@ extern "C" int fs_upsample_warp3d_pair_bwd(const float* img0, const float* img1,
                                            float* ws, int B, int C, const int* in_dhw, int Ds, int Hs, int Ws,
                                            int factor, float scale, fs_stream_t stream) {
   FS_REQUIRE_PTR(grad_delta); FS_REQUIRE_PTR(ws);
-  if (factor != 2 && factor != 4) return FS_ERR_ARG;
-  if (Ds < 1 || Hs < 1 || Ws < 1) return FS_ERR_SHAPE;
-  if ((long long)Ds * Hs * Ws * factor * factor * factor >= (1ll << 31)) return FS_ERR_SHAPE;
-  const int D = Ds * factor, H = Hs * factor, W = Ws * factor;
-  int rc = fs_warp3d_pair_bwd_acc(img0, img1, flow6, grad_out0, grad_out1, nullptr, nullptr, grad_flow_add,
-                                  grad_flow_total, B, C, in_dhw, D, H, W, stream);
+  W3P p;
+  if (const int rc = make_params_up(p, B, C, in_dhw, Ds, Hs, Ws, factor); rc != FS_OK) return rc;
+  const int rc = fs_warp3d_pair_bwd_acc(img0, img1, flow6, grad_out0, grad_out1, nullptr, nullptr, grad_flow_add, grad_flow_total,
+                                        B, C, in_dhw, p.D, p.H, p.W, stream);
   if (rc != FS_OK) return rc;
-  return fs_interp3d_bwd_scaled(grad_flow_total, grad_delta, ws, B, 6, Ds, Hs, Ws, D, H, W, factor, 1, scale,
-                                stream);
+  return fs_interp3d_bwd_scaled(grad_flow_total, grad_delta, ws, B, 6, Ds, Hs, Ws, p.D, p.H, p.W, factor, 1, scale, stream);
 }

@@ -15,6 +15,7 @@ Row fields:
   why     the rung of the ladder the row is on
 
 Shapes are as small as their rung allows; the rows on the two sides of a threshold differ in one quantity only."""
+from ledger_harness import normalize  # noqa: F401  (a ledger carries the naming of its kernels)
 
 FORMS = ("fwd", "fwd_add", "fwd_prelu", "fwd_dprelu", "fwd_ms", "tr", "tr_add", "tr_prelu", "wrw", "wrw_det", "wrw_ms")
 
@@ -243,25 +244,6 @@ PLAN_OF = {
 
 def plan_of(kernel):
     return PLAN_OF[kernel] if kernel in PLAN_OF else PLAN_OF[kernel.split("<")[0]]
-
-
-def normalize(name):
-    """A demangled kernel name as ops._KERNELS writes symbols: no `void `, no anonymous namespace, no argument list."""
-    name = name.strip()
-    if name.startswith("void "):
-        name = name[5:]
-    name = name.replace("(anonymous namespace)::", "")
-    if name.endswith(".kd"):
-        name = name[:-3]
-    depth = 0
-    for i, ch in enumerate(name):  # cut at the first '(' outside template brackets
-        if ch == "<":
-            depth += 1
-        elif ch == ">":
-            depth -= 1
-        elif ch == "(" and depth == 0:
-            return name[:i].strip()
-    return name
 
 
 def row_id(r):

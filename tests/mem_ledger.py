@@ -34,7 +34,7 @@ What reading the dispatch code against its operands decided (the rows pin each o
 
 Out of scope here (the next ledgers): warp2d.hip, corr2d.hip, corr3d.hip, losses.hip, laplacian*.hip, epilogue.hip,
 prelu.hip, census3d.hip, flowsmooth3d.hip and the metrics sources (metrics.hip, flowmetrics.hip, wssim.hip, series.hip)."""
-from conv_ledger import normalize as _normalize
+from ledger_harness import normalize as _normalize
 
 ROWS = []
 
@@ -63,7 +63,7 @@ BWD_OPS = ("w_bwd", "wp_bwd", "wp_acc", "wp_acc3", "uw_bwd", "uw_bwd3")
 
 
 def normalize(name):
-    """conv_ledger.normalize, and no `rc::` (ops._KERNELS writes the row-cache kernels without their namespace)."""
+    """ledger_harness.normalize, and no `rc::` (ops._KERNELS writes the row-cache kernels without their namespace)."""
     return _normalize(name).replace("rc::", "")
 
 

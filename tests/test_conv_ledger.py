@@ -6,54 +6,25 @@ unreachable entry whose kernel no longer exists.  Plan agreement: for every row,
 fs_conv3d_{fwd,tr}_wprep_jobs, the FS_WRW_KERNEL_* id of fs_conv3d_wrw_kernel_id, both asked with placeholder pointers
 that carry the row's misalignments) is the one of the row's kernel."""
 import os
-import re
-import shutil
-import subprocess
 import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "opticalflowscivis_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_ledger as L  # noqa: E402
+import ledger_harness as H  # noqa: E402
 
 SOURCES = ("convfwd.hip", "convtr.hip", "convwrw.hip")
 
 
-def _kernels_of(src):
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-           "-S", "--cuda-device-only", os.path.join(CSRC, src), "-o", "-"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    mangled = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", r.stdout, flags=re.M)
-    d = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True)
-    return {L.normalize(n) for n in d.stdout.splitlines() if n.strip()}
-
-
 @pytest.fixture(scope="module")
 def compiled():
-    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
-        pytest.skip("needs hipcc")
-    if not shutil.which("c++filt"):
-        pytest.skip("needs c++filt")
-    with ThreadPoolExecutor(len(SOURCES)) as ex:
-        sets = list(ex.map(_kernels_of, SOURCES))
-    return set().union(*sets)
+    return H.compiled_kernels(SOURCES, L.normalize)
 
 
 def test_every_compiled_kernel_has_a_row(compiled):
-    expected = {r["kernel"] for r in L.ROWS}
-    both = expected & set(L.UNREACHABLE_IN_PRODUCT)
-    assert not both, "kernels both reached by a row and listed as unreachable: %s" % sorted(both)
-    compute = compiled - L.HELPERS
-    missing = sorted(compute - expected - set(L.UNREACHABLE_IN_PRODUCT))
-    stale = sorted((expected | set(L.UNREACHABLE_IN_PRODUCT)) - compute)
-    assert not missing, "compiled compute kernels without a ledger row: %s" % missing
-    assert not stale, "ledger kernels the build no longer compiles: %s" % stale
-    assert L.HELPERS <= compiled, "helpers no longer compiled: %s" % sorted(L.HELPERS - compiled)
+    H.assert_complete(compiled, {r["kernel"] for r in L.ROWS}, L.UNREACHABLE_IN_PRODUCT, L.HELPERS)
 
 
 def test_rows_are_well_formed():

@@ -12,7 +12,6 @@ aligned with FS_ERR_ARG, and nothing is written (the refusal is host code in fro
 import ctypes
 import math
 import os
-import subprocess
 import sys
 import time
 
@@ -22,76 +21,23 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_ledger as LG  # noqa: E402
+from ledger_harness import DEV, Guarded, kernels_launched, load_lib, on_device, stream as _stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
-GUARD = 4096
-NAN_BITS = 0x7FC0DEAD  # a quiet NaN no kernel produces
 TOL = 2e-5
 FS_ERR_ARG = 3
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from opticalflowscivis_amd import _lib
-    return _lib.lib()
-
-
-class Guarded:
-    """n floats, 16-byte aligned, between two guard bands of NAN_BITS; the interior starts as NAN_BITS too (an output
-    element the kernel never writes then fails the comparison), or zero."""
-
-    def __init__(self, n, zero=False):
-        self.n = int(n)
-        self.buf = torch.empty(self.n + 2 * GUARD, dtype=torch.float32, device=DEV)
-        self.buf.view(torch.int32).fill_(NAN_BITS)
-        self.t = self.buf[GUARD:GUARD + self.n]
-        assert self.t.data_ptr() % 16 == 0
-        if zero:
-            self.t.zero_()
-
-    def ptr(self, offset=0):
-        return self.t.data_ptr() + 4 * offset
-
-    def intact(self):
-        b = self.buf.view(torch.int32)
-        return bool((b[:GUARD] == NAN_BITS).all()) and bool((b[GUARD + self.n:] == NAN_BITS).all())
-
-    def view(self, shape):
-        return self.t.view(shape)
-
-
-def on_device(t, mis=0):
-    """`t` on the GPU as a contiguous view starting `mis` floats past a 16-byte boundary."""
-    buf = torch.empty(t.numel() + 4, dtype=torch.float32, device=DEV)
-    v = buf[mis:mis + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == 4 * mis
-    return v
-
-
-def _stream():
-    return torch.cuda.current_stream(DEV).cuda_stream
+    return load_lib()
 
 
 def _conv_kernels_launched(fn):
-    """(fn's return value, normalized names of the convolution kernels it launched) -- torch.profiler's device
-    activity, which records launches from the ctypes-loaded library as well."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        rc = fn()
-        torch.cuda.synchronize()
-    raw = [e.name for e in prof.events()]
-    mangled = sorted({n for n in raw if n.startswith("_Z")})
-    if mangled:  # (a tracer that reports mangled names)
-        out = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout
-        raw = [dict(zip(mangled, out.splitlines())).get(n, n) for n in raw]
-    names = [LG.normalize(n) for n in raw]
-    return rc, [n for n in names if n.startswith("conv3d_") or n.startswith("convtr_") or n in LG.HELPERS]
+    """(fn's return value, normalized names of the convolution kernels it launched)."""
+    return kernels_launched(fn, LG.normalize,
+                            lambda n: n.startswith("conv3d_") or n.startswith("convtr_") or n in LG.HELPERS)
 
 
 def _rel(got, ref):
@@ -366,4 +312,4 @@ def test_misaligned_output_is_refused(lib, case):
     assert rc == FS_ERR_ARG, rc
     assert launched == [], launched
     for name, b in bufs.items():
-        assert bool((b.buf.view(torch.int32) == NAN_BITS).all()), "%s was written" % name
+        assert b.untouched(), "%s was written" % name

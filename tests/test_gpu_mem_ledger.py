@@ -13,7 +13,6 @@ those by name and require equal bits.  A summary line per row (kernels, errors o
 The argument errors these entry points define are refused with their status before anything is launched or written."""
 import ctypes
 import os
-import subprocess
 import sys
 import time
 
@@ -22,13 +21,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mem_ledger as LG  # noqa: E402
+from ledger_harness import DEV, Guarded, kernels_launched, load_lib, on_device, stream as _stream  # noqa: E402
 import mem_ledger_inputs as I  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
-GUARD = 4096
-NAN_BITS = 0x7FC0DEAD  # a quiet NaN no kernel produces
 FS_ERR_NULLPTR, FS_ERR_ARG = 1, 3
 WIDE = 11  # channels of the wider tensors the strided operands are slices of
 # how the kernels of the two sources are named: a launched kernel of that kind that is not a ledger symbol is an error
@@ -38,44 +35,7 @@ KNOWN = {k for r in LG.ROWS for k in LG.kernels_of(r)} | set(LG.UNREACHABLE_IN_P
 
 @pytest.fixture(scope="module")
 def lib():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from opticalflowscivis_amd import _lib
-    return _lib.lib()
-
-
-class Guarded:
-    """n floats starting `mis` floats past a 16-byte boundary, between two guard bands of NAN_BITS; the interior starts as
-    NAN_BITS too (an output element the kernel never writes then fails the comparison), or zero."""
-
-    def __init__(self, n, zero=False, mis=0):
-        self.n = int(n)
-        self.buf = torch.empty(self.n + 2 * GUARD + 4, dtype=torch.float32, device=DEV)
-        self.buf.view(torch.int32).fill_(NAN_BITS)
-        self.lo = GUARD + mis
-        self.t = self.buf[self.lo:self.lo + self.n]
-        assert self.t.data_ptr() % 16 == 4 * mis
-        if zero:
-            self.t.zero_()
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def intact(self):
-        b = self.buf.view(torch.int32)
-        return bool((b[:self.lo] == NAN_BITS).all()) and bool((b[self.lo + self.n:] == NAN_BITS).all())
-
-    def untouched(self):
-        return bool((self.buf.view(torch.int32) == NAN_BITS).all())
-
-
-def on_device(t, mis=0):
-    """`t` on the GPU as a contiguous view starting `mis` floats past a 16-byte boundary."""
-    buf = torch.empty(t.numel() + 4, dtype=torch.float32, device=DEV)
-    v = buf[mis:mis + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == 4 * mis
-    return v
+    return load_lib()
 
 
 def slice_of_wide(t, c0, mis=0, odd_stride=False):
@@ -93,28 +53,10 @@ def slice_of_wide(t, c0, mis=0, odd_stride=False):
     return v, bs
 
 
-def _stream():
-    return torch.cuda.current_stream(DEV).cuda_stream
-
-
 def _kernels_launched(fn):
-    """(fn's return value, normalized names of the warp3d.hip / interp.hip kernels it launched) -- torch.profiler's
-    device activity, which records launches from the ctypes-loaded library as well."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        rc = fn()
-        torch.cuda.synchronize()
-    raw = [e.name for e in prof.events()]
-    mangled = sorted({n for n in raw if n.startswith("_Z")})
-    if mangled:  # (a tracer that reports mangled names)
-        out = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout
-        raw = [dict(zip(mangled, out.splitlines())).get(n, n) for n in raw]
-    names = [LG.normalize(n) for n in raw]
-    ours = [n for n in names if n in KNOWN or n.startswith(PREFIXES)]
-    strangers = sorted(set(ours) - KNOWN)
-    assert not strangers, "kernels of warp3d.hip / interp.hip that the ledger does not know: %s" % strangers
-    return rc, ours
+    """(fn's return value, normalized names of the warp3d.hip / interp.hip kernels it launched); one the ledger does not
+    know is an error."""
+    return kernels_launched(fn, LG.normalize, lambda n: n in KNOWN or n.startswith(PREFIXES), KNOWN)
 
 
 def _dhw(ext):
