@@ -47,8 +47,10 @@ enum {
  *   340  fs_frame_metrics2d / fs_frame_metrics3d and their _ws_bytes queries (sequence evaluation: PSNR / SSIM).
  *   350  fs_flow_metrics2d / fs_flow_metrics3d and their _ws_bytes queries (flow accuracy: EPE, Fl, angular error).
  *   360  fs_triplet_gather, fs_series_stats / fs_series_stats_ws_bytes (training batches from a device-resident series).
- *   370  fs_census3d_dist_{fwd,bwd}, fs_flow_smooth3d_{fwd,bwd} (unsupervised flow-side loss terms of Flow-3D). */
-#define FS_ABI_VERSION 370
+ *   370  fs_census3d_dist_{fwd,bwd}, fs_flow_smooth3d_{fwd,bwd} (unsupervised flow-side loss terms of Flow-3D).
+ *   380  fs_flow_consistency2d / fs_flow_consistency3d and their _ws_bytes queries (label-free flow quality:
+ *        forward-backward residual, occlusion / outgoing / consistent classes, photometric error of the warp). */
+#define FS_ABI_VERSION 380
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -706,6 +708,51 @@ int fs_flow_metrics2d(const float* pred, const float* gt, int N, int C, int H, i
 int fs_flow_metrics3d(const float* pred, const float* gt, int N, int C, int D, int H, int W, long long pred_bstride,
                       long long gt_bstride, const unsigned char* valid, const unsigned char* noc, int convention,
                       float tau_abs, float tau_rel, float* epe_map, double* ws, double* out, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Forward-backward consistency -- the label-free quality measure of a flow: N pairs of displacements, one launch.
+ *   flow_f, flow_b: N flows of C fp32 planes of D*H*W (2-D: D = 1, C = 2; 3-D: C = 3) elements each, laid out and
+ *     strided exactly as fs_flow_metrics*'s operands (planes of one flow contiguous, flow n at + n * bstride elements,
+ *     bstride >= C*D*H*W when N > 1; channel 0 along W, 1 along H, 2 along D, in elements).  flow_f maps frame a to
+ *     frame b on a's grid, flow_b maps b to a on b's grid.
+ *   img0, img1: fp32 [N, D, H, W] (contiguous) frames a and b, both or neither (NULL).
+ *   valid: uint8 [N, D, H, W] (contiguous, nonzero = set) or NULL = every element is valid.
+ *   Per element x, in fp64 without fused multiply-adds (a restatement with the same operations in the same order
+ *   reproduces every count exactly):
+ *     p_c = x_c + flow_f_c(x).  A non-finite flow_f_c(x): NONFINITE.  Else p_c < 0 or p_c > S_c - 1 for some c:
+ *     OUTGOING (the border is inclusive; an extent of 1 is legal).  Else i0 = floor(p_c), f_c = p_c - i0,
+ *     g_c = 1 - f_c, i1 = min(i0 + 1, S_c - 1); the corner with bits (bz, by, bx) weighs (tz * ty) * tx (2-D: ty * tx),
+ *     t = f where the bit is set, else g; Fbw_c = the sum over the corners in ascending 4 bz + 2 by + bx, from 0.0, of
+ *     weight * flow_b_c[corner], every product formed (a non-finite corner of weight 0 gives NaN); I1w likewise from
+ *     img1.  r2 = sum_c (flow_f_c + Fbw_c)^2, m2 = sum_c flow_f_c^2 + sum_c Fbw_c^2 (each sum in ascending c from
+ *     0.0), r = sqrt(r2), e = I1w - img0(x).  Fbw, or with images img0(x) or I1w, not finite: NONFINITE.  Else
+ *     OCCLUDED when r2 > alpha1 * m2 + alpha2 (UnFlow: 0.01, 0.5), CONSISTENT otherwise.  inside = OCCLUDED + CONSISTENT.
+ *   out: fp64 [N][FS_FLOW_CONSISTENCY_K], over the elements with `valid` set:
+ *     0 n_valid   1 n_nonfinite   2 n_outgoing   3 n_occluded   4 n_consistent
+ *     5 sum r (inside)   6 sum r2 (inside)   7 max r (inside; -inf when none)   8 sum r (consistent)
+ *     9 sum |e| (inside)  10 sum e^2 (inside)  11 sum |e| (consistent)  12 sum e^2 (consistent)   (9-12: 0 without images)
+ *   class_map: uint8 [N, D, H, W] or NULL: 0 where valid is not set, else the FS_FC_* class.
+ *   res_map: fp32 [N, D, H, W] or NULL: r at EVERY element, valid or not; NaN where it is outgoing or nonfinite.
+ *   Per-workgroup fp64 partials in `ws` (fs_flow_consistency{2,3}d_ws_bytes bytes, 8-byte aligned), summed by a second
+ *   launch in a fixed order: bitwise reproducible, no atomics.
+ *   FS_ERR_NULLPTR: flow_f, flow_b, ws or out NULL.  FS_ERR_SHAPE: N < 1, C other than 2 (2-D) / 3 (3-D), an extent
+ *   < 1, a batch stride below C*D*H*W.  FS_ERR_ARG: alpha1 or alpha2 negative or not finite, exactly one image given.
+ *   All of them are returned before anything is launched.  The _ws_bytes queries launch nothing and return the byte
+ *   count or -(FS_ERR_*).
+ */
+#define FS_FLOW_CONSISTENCY_K 13
+#define FS_FC_MAX_R 7
+enum { FS_FC_NOT_VALID = 0, FS_FC_CONSISTENT = 1, FS_FC_OCCLUDED = 2, FS_FC_OUTGOING = 3, FS_FC_NONFINITE = 4 };
+long long fs_flow_consistency2d_ws_bytes(int N, int C, int H, int W);
+long long fs_flow_consistency3d_ws_bytes(int N, int C, int D, int H, int W);
+int fs_flow_consistency2d(const float* flow_f, const float* flow_b, int N, int C, int H, int W, long long f_bstride,
+                          long long b_bstride, const float* img0, const float* img1, const unsigned char* valid,
+                          double alpha1, double alpha2, unsigned char* class_map, float* res_map, double* ws,
+                          double* out, fs_stream_t stream);
+int fs_flow_consistency3d(const float* flow_f, const float* flow_b, int N, int C, int D, int H, int W,
+                          long long f_bstride, long long b_bstride, const float* img0, const float* img1,
+                          const unsigned char* valid, double alpha1, double alpha2, unsigned char* class_map,
+                          float* res_map, double* ws, double* out, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

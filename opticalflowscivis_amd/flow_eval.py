@@ -15,7 +15,24 @@ one flow_metrics launch.
 
 --seq takes a [T,H,W] (2-D) or [T,D,H,W] (3-D) array in [0,1] and --gt a [T,C,*spatial] array of per-frame velocities
 (elements per frame, channel 0 along W): gt(a, b) = velocity[a] * (b - a), exact for steady motion, every finite
-element valid, no occlusion split."""
+element valid, no occlusion split.
+
+--consistency adds the label-free measure (ops.flow_consistency: forward-backward residual, occluded / outgoing /
+consistent fractions, photometric error of the flow-warped frame; thresholds --alpha A1 A2) and makes --seq legal
+without --gt: a series with no known motion is scored by consistency alone and the result has no accuracy section.
+
+    python -m opticalflowscivis_amd.flow3d.evaluate_flow --seq frames.npy --consistency --out r.json
+
+No extra inference is run.  UPFlow's flow_f_out / flow_b_out of a pair are each other's opposite.  A RIFE model's pair
+(t, t+g), g = 2h, yields flows that start at its mid frame, so the opposite flows come from neighbouring pairs
+(rife_consistency_pairs): for every m with m-h >= 0 and m+2h <= T-1 the flow m -> m+h is F_mid->1 of pair m-h and the
+flow m+h -> m is F_mid->0 of pair m.  Both directions are scored (the backward one is the same call with flows and
+frames swapped), with the two frames as images.  With a ground truth, every scored direction also reports epe_est_noc /
+epe_est_occ: flow_metrics of that flow with the ESTIMATED consistent mask in place of the generator's noc.  A flow
+and its consistency classes live on the same grid for every flow scored here (UPFlow's t0->t1 on t0 and t1->t0 on t1;
+RIFE's m -> m+h on frame m = the mid frame of pair m-h, m+h -> m on frame m+h = the mid frame of pair m); the RIFE
+flows that have no opposite flow in the sequence -- F_mid->0 of the first h pairs and F_mid->1 of the last h pairs --
+are in no consistency pair and get no epe_est_* entry."""
 import argparse
 import json
 import os
@@ -63,6 +80,65 @@ def rife_pairs(T, gap):
     if gap < 2 or gap % 2:
         raise ValueError("the RIFE models score the mid frame of (t, t+g): g must be even, got %d" % gap)
     return [(t, t + gap) for t in range(0, T - gap)]
+
+
+def rife_consistency_pairs(T, gap):
+    """[(m, m+h, i_fwd, i_bwd)], h = gap / 2, for a RIFE model run on rife_pairs(T, gap): i_fwd / i_bwd index the
+    [2P, C, *sp] stack of rife_flows (2t = F_mid->0 and 2t + 1 = F_mid->1 of pair t = (t, t+gap)).  The flow m -> m+h
+    is the second flow of pair m-h (mid frame m), the flow m+h -> m the first flow of pair m (mid frame m+h); both
+    exist for m-h >= 0 and m+2h <= T-1.  Empty when the sequence is too short."""
+    if gap < 2 or gap % 2:
+        raise ValueError("the RIFE models score the mid frame of (t, t+g): g must be even, got %d" % gap)
+    h = gap // 2
+    return [(m, m + h, 2 * (m - h) + 1, 2 * m) for m in range(h, T - gap)]
+
+
+CONSISTENCY_STATS = ("fb_mean", "fb_rmse", "fb_max", "fb_mean_noc", "occ_frac", "out_frac", "warp_l1", "warp_l1_noc",
+                     "warp_psnr", "warp_psnr_noc", "n_valid", "n_inside", "n_noc", "n_occ", "n_out", "n_nonfinite")
+
+
+def _nanmean(vals):
+    vals = [v for v in vals if not np.isnan(v)]
+    return float(np.mean(vals)) if vals else float("nan")
+
+
+def evaluate_consistency(pred, frames, cpairs, alpha, gt=None, save_dir=None):
+    """Forward-backward consistency of `pred` [P,C,*sp] (displacements) for `cpairs` = [(t_a, t_b, i_ab, i_ba)]: the
+    flow t_a -> t_b is pred[i_ab] on frame t_a's grid, its opposite pred[i_ba] on frame t_b's.  Both directions of
+    every pair go through one flow_consistency launch.  `gt`: also epe_est_noc / epe_est_occ per direction (a second
+    flow_metrics launch with the estimated consistent mask as noc).  `save_dir`: class_%03d_to_%03d.npy per direction."""
+    doc = {"alpha": [float(alpha[0]), float(alpha[1])], "pairs": [], "mean": {}}
+    if not cpairs:
+        return doc
+    dirs = []  # (t_from, t_to, index of the flow, index of its opposite)
+    for a, b, iab, iba in cpairs:
+        dirs += [(a, b, iab, iba), (b, a, iba, iab)]
+    dev = pred.device
+    idx = lambda k: torch.tensor([d[k] for d in dirs], device=dev)
+    ff, fb = pred.index_select(0, idx(2)), pred.index_select(0, idx(3))
+    fr = frames.to(torch.float32)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = ops.flow_consistency(ff, fb, fr.index_select(0, idx(0)), fr.index_select(0, idx(1)), None, alpha,
+                               return_maps=gt is not None or save_dir is not None)
+    torch.cuda.synchronize()
+    doc["time_consistency_s"] = time.perf_counter() - t0
+    rows = [dict({k: float(res[k][i]) for k in CONSISTENCY_STATS}, t_from=d[0], t_to=d[1]) for i, d in enumerate(dirs)]
+    keys = list(CONSISTENCY_STATS)
+    if gt is not None:
+        disp, valid, _ = gt_stack(gt, [(d[0], d[1]) for d in dirs])
+        est = ops.flow_metrics(ff, disp, valid, res["noc"], "disp")
+        for i, r in enumerate(rows):
+            r["epe_est_noc"], r["epe_est_occ"] = float(est["epe_noc"][i]), float(est["epe_occ"][i])
+        keys += ["epe_est_noc", "epe_est_occ"]
+    if save_dir:
+        os.makedirs(save_dir, exist_ok=True)
+        c = res["class_map"].cpu().numpy()
+        for i, d in enumerate(dirs):
+            np.save(os.path.join(save_dir, "class_%03d_to_%03d.npy" % (d[0], d[1])), c[i])
+    doc["pairs"] = rows
+    doc["mean"] = {k: _nanmean([r[k] for r in rows]) for k in keys}
+    return doc
 
 
 def _final_flow(model, a, b):
@@ -155,7 +231,7 @@ def _common_args(nd, desc):
     ap = argparse.ArgumentParser(description=desc)
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--dataset", choices=DATASETS[nd], help="synthetic sequence with known motion")
-    src.add_argument("--seq", help=".npy sequence [T,%s] in [0,1] (needs --gt)" % ",".join("DHW"[3 - nd:]))
+    src.add_argument("--seq", help=".npy sequence [T,%s] in [0,1] (needs --gt or --consistency)" % ",".join("DHW"[3 - nd:]))
     ap.add_argument("--gt", help=".npy per-frame velocities [T,%d,%s] for --seq" % (nd, ",".join("DHW"[3 - nd:])))
     ap.add_argument("--frames", type=int, default=9, help="frames of a synthetic sequence")
     ap.add_argument("--size", type=int, nargs="+", default=None, help="synthetic extent (S, or H W in 2-D)")
@@ -166,14 +242,32 @@ def _common_args(nd, desc):
     ap.add_argument("--zero-baseline", action="store_true", help="also score a zero displacement")
     ap.add_argument("--save-flows", default=None, metavar="DIR", help="write every predicted flow (as a displacement) as .npy here")
     ap.add_argument("--out", default=None, help="write the results as JSON here")
+    ap.add_argument("--consistency", action="store_true",
+                    help="also score forward-backward consistency (needs no ground truth: makes --seq legal without --gt)")
+    ap.add_argument("--alpha", type=float, nargs=2, default=(0.01, 0.5), metavar=("A1", "A2"),
+                    help="occluded when |Ff + Fb(x + Ff)|^2 > A1 (|Ff|^2 + |Fb|^2) + A2")
     return ap
+
+
+def check_args(args):
+    """What the parser cannot express: --seq needs --gt unless --consistency gives the run something to measure."""
+    if args.seq and not args.gt and not args.consistency:
+        raise SystemExit("--seq needs --gt (per-frame velocities)")
+    if args.seq and not args.gt and args.zero_baseline:
+        raise SystemExit("--zero-baseline needs a ground truth (--gt)")
+    if not (0 <= args.alpha[0] < float("inf") and 0 <= args.alpha[1] < float("inf")):
+        raise SystemExit("--alpha takes two finite values >= 0")
+    return args
 
 
 def _sequence(args, nd, dev):
     if args.seq:
-        if not args.gt:
-            raise SystemExit("--seq needs --gt (per-frame velocities)")
+        check_args(args)
         frames = torch.from_numpy(np.load(args.seq).astype(np.float32)).to(dev)
+        if not args.gt:  # --consistency alone: no known motion
+            if frames.dim() != nd + 1:
+                raise ValueError("--seq must be [T,%s], got %s" % (",".join("DHW"[3 - nd:]), tuple(frames.shape)))
+            return frames, None, os.path.basename(args.seq)
         vel = torch.from_numpy(np.load(args.gt).astype(np.float32)).to(dev)
         if frames.dim() != nd + 1 or tuple(vel.shape) != (frames.shape[0], nd) + tuple(frames.shape[1:]):
             raise ValueError("--seq must be [T,%s] and --gt [T,%d,%s], got %s and %s" % (
@@ -185,12 +279,26 @@ def _sequence(args, nd, dev):
 
 def _finish(doc, args, frames, name, t_inf):
     doc.update(sequence=name, shape=list(frames.shape), gap=args.gap, batch=args.batch, time_inference_s=t_inf)
-    m = doc["mean"]
-    line = "%s gap %d: EPE %.4f (noc %.4f, occ %.4f)  Fl %.4f  AE %.3f deg  RMSE %.4f" % (
-        name, args.gap, m["epe"], m["epe_noc"], m["epe_occ"], m["fl"], m["ae_deg"], m["rmse"])
-    if "zero_baseline" in doc:
-        line += "  | zero flow EPE %.4f" % doc["zero_baseline"]["mean"]["epe"]
-    print(line + "  | inference %.3f s  metrics %.4f s" % (t_inf, doc["time_metrics_s"]))
+    if "mean" in doc:
+        m = doc["mean"]
+        line = "%s gap %d: EPE %.4f (noc %.4f, occ %.4f)  Fl %.4f  AE %.3f deg  RMSE %.4f" % (
+            name, args.gap, m["epe"], m["epe_noc"], m["epe_occ"], m["fl"], m["ae_deg"], m["rmse"])
+        if "zero_baseline" in doc:
+            line += "  | zero flow EPE %.4f" % doc["zero_baseline"]["mean"]["epe"]
+        print(line + "  | inference %.3f s  metrics %.4f s" % (t_inf, doc["time_metrics_s"]))
+    if "consistency" in doc:
+        c = doc["consistency"]
+        m = c["mean"]
+        if not c["pairs"]:
+            print("%s gap %d: the sequence is too short for a forward-backward pair" % (name, args.gap))
+        else:
+            line = ("%s gap %d: FB residual %.4f (noc %.4f, max %.4f)  occluded %.4f  outgoing %.4f  warp L1 %.5f  "
+                    "PSNR %.2f dB" % (name, args.gap, m["fb_mean"], m["fb_mean_noc"], m["fb_max"], m["occ_frac"],
+                                      m["out_frac"], m["warp_l1"], m["warp_psnr"]))
+            if "epe_est_noc" in m:
+                line += "  | EPE est. noc %.4f, est. occ %.4f" % (m["epe_est_noc"], m["epe_est_occ"])
+            print(line + "  | %d flows  inference %.3f s  consistency %.4f s" % (len(c["pairs"]), t_inf,
+                                                                               c["time_consistency_s"]))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
@@ -200,7 +308,7 @@ def _finish(doc, args, frames, name, t_inf):
 
 def main_rife(Model, nd, argv=None):
     """flow2d / flow3d: the final IFNet flow at the mid frame of (t, t+gap)."""
-    args = _common_args(nd, "score the flows of a RIFE model against known motion").parse_args(argv)
+    args = check_args(_common_args(nd, "score the flows of a RIFE model against known motion").parse_args(argv))
     dev = torch.device("cuda")
     model = Model(-1, device=dev)
     try:
@@ -219,11 +327,14 @@ def main_rife(Model, nd, argv=None):
     pred = rife_flows(model, frames, pairs, args.batch)
     torch.cuda.synchronize()
     t_inf = time.perf_counter() - t0
-    doc = evaluate_flows(pred, targets, gt, "disp", ["mid->t0", "mid->t1"], pairs, args.zero_baseline)
+    doc = evaluate_flows(pred, targets, gt, "disp", ["mid->t0", "mid->t1"], pairs, args.zero_baseline) if gt else {}
     doc["model"] = args.model
     doc["model_flow"] = "rife3d, converted at the padded extents" if nd == 3 else "disp"
     if args.save_flows:
         _save(args.save_flows, pred, targets)
+    if args.consistency:
+        doc["consistency"] = evaluate_consistency(pred, frames, rife_consistency_pairs(frames.shape[0], args.gap),
+                                                  args.alpha, gt, args.save_flows)
     return _finish(doc, args, frames, name, t_inf)
 
 
@@ -231,7 +342,7 @@ def main_upflow(make_net, argv=None):
     """upflow: flow_f_out of (t, t+gap) and flow_b_out of (t+gap, t)."""
     ap = _common_args(2, "score UPFlow's forward and backward flows against known motion")
     ap.set_defaults(gap=1)
-    args = ap.parse_args(argv)
+    args = check_args(ap.parse_args(argv))
     if args.gap < 1:
         raise SystemExit("--gap must be >= 1")
     net = make_net(args.model)
@@ -246,8 +357,12 @@ def main_upflow(make_net, argv=None):
     pred = upflow_flows(net, frames, pairs, args.batch)
     torch.cuda.synchronize()
     t_inf = time.perf_counter() - t0
-    doc = evaluate_flows(pred, targets, gt, "disp", ["t0->t1", "t1->t0"], pairs, args.zero_baseline)
+    doc = evaluate_flows(pred, targets, gt, "disp", ["t0->t1", "t1->t0"], pairs, args.zero_baseline) if gt else {}
     doc["model"] = args.model
     if args.save_flows:
         _save(args.save_flows, pred, targets)
+    if args.consistency:
+        # both directions of (2i, 2i + 1) are scored: one entry per pair
+        doc["consistency"] = evaluate_consistency(pred, frames, [(a, b, 2 * i, 2 * i + 1) for i, (a, b) in
+                                                                  enumerate(pairs)], args.alpha, gt, args.save_flows)
     return _finish(doc, args, frames, name, t_inf)

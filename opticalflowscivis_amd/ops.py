@@ -2549,6 +2549,139 @@ def _flow_stats(out, split, emap):
 
 
 # --------------------------------------------------------------------------------------------
+# Flow quality without ground truth: forward-backward consistency and the photometric error of the warp
+# (fs_flow_consistency{2,3}d)
+# --------------------------------------------------------------------------------------------
+FLOW_CONSISTENCY_K = 13  # FS_FLOW_CONSISTENCY_K: the per-pair sums, in the order include/flowsci_hip.h documents
+FC_NOT_VALID, FC_CONSISTENT, FC_OCCLUDED, FC_OUTGOING, FC_NONFINITE = 0, 1, 2, 3, 4  # FS_FC_*: class_map codes
+_CONSISTENCY_KEYS = ("fb_mean", "fb_rmse", "fb_max", "fb_mean_noc", "occ_frac", "out_frac", "warp_l1", "warp_l1_noc",
+                     "warp_psnr", "warp_psnr_noc", "n_valid", "n_inside", "n_noc", "n_occ", "n_out", "n_nonfinite")
+
+
+def flow_consistency_cost(shape, images=True, maps=False):
+    """(HBM bytes, flops) the algorithm needs for one flow_consistency call on [N,C,*spatial] flow pairs: both flows
+    read once (the 2^C corner reads of flow_b overlap between neighbours: each of its elements is needed about once),
+    both frames once if given, the uint8 class map and the fp32 residual map written once if asked.  Flops per element:
+    the 2^C corner weights (C - 1 products each), 2 per corner and gathered plane, ~8 C for the sums and the test."""
+    n = 1
+    for s in shape:
+        n *= int(s)
+    C = int(shape[1])
+    elems = n // C
+    planes = C + (1 if images else 0)
+    flops = (1 << C) * (C - 1) + 2 * (1 << C) * planes + 8 * C + (6 if images else 0)
+    return 2 * 4 * n + (2 * 4 * elems if images else 0) + (5 * elems if maps else 0), flops * elems
+
+
+def _flow_image(name, t, shape, device):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s must be a tensor or None" % name)
+    if not t.is_cuda:
+        raise ValueError("%s must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (name, t.device))
+    if t.device != device:
+        raise ValueError("%s must be on the flows' device %s, got %s" % (name, device, t.device))
+    if t.dim() == len(shape) + 1 and t.shape[1] == 1:
+        t = t[:, 0]
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be [N,*spatial] = %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t.to(torch.float32).contiguous()
+
+
+def flow_consistency(flow_f, flow_b, img0=None, img1=None, valid=None, alpha=(0.01, 0.5), return_maps=False):
+    """Label-free quality of N flow pairs, one launch (fs_flow_consistency{2,3}d): the forward-backward residual, the
+    occluded / outgoing / consistent classes it implies and the photometric error of the flow-warped frame.
+
+    flow_f, flow_b: [N,2,H,W] or [N,3,D,H,W] displacements in elements (channel 0 along W, 1 along H, 2 along D) on a
+    GPU, operands as flow_metrics takes them (a channel slice is read in place).  flow_f maps frame a to frame b on
+    a's grid, flow_b maps b to a on b's grid; the other direction is the same call with flows and frames swapped.
+    img0, img1: optional frames a and b, [N,*sp] (or [N,1,*sp]), both or neither.  valid: optional bool / uint8 [N,*sp].
+    alpha = (alpha1, alpha2): with Fbw = flow_b sampled (bi- / trilinearly) at x + flow_f(x), an element is occluded
+    when |flow_f + Fbw|^2 > alpha1 (|flow_f|^2 + |Fbw|^2) + alpha2 (UnFlow's test and thresholds), consistent (noc)
+    otherwise; it is outgoing when x + flow_f(x) leaves the grid (border inclusive) and nonfinite when flow_f(x), Fbw or
+    (with images) img0(x) or the sampled img1 is not finite.  inside = occluded + consistent.
+
+    Returns a dict of fp64 [N] tensors: fb_mean, fb_rmse, fb_max (the residual |flow_f + Fbw| over inside), fb_mean_noc,
+    occ_frac = n_occ / n_inside, out_frac = n_out / n_valid, warp_l1, warp_l1_noc (mean |img1 warped - img0| over inside /
+    noc), warp_psnr, warp_psnr_noc (-10 log10 of the mean squared error: frames in [0,1]; the four are NaN without
+    images), n_valid, n_inside, n_noc, n_occ, n_out, n_nonfinite.  A ratio with an empty denominator is NaN.  With
+    return_maps=True also class_map (uint8 [N,*sp]: 0 not valid, 1 consistent, 2 occluded, 3 outgoing, 4 nonfinite),
+    res_map (fp32 [N,*sp]: the residual at every element, NaN where outgoing or nonfinite) and noc (bool,
+    class_map == 1: the mask flow_metrics takes as `noc`).  A measurement on detached values: nothing is differentiated."""
+    if not isinstance(flow_f, torch.Tensor) or flow_f.dim() not in (4, 5):
+        raise ValueError("flow_f must be [N,2,H,W] or [N,3,D,H,W], got %s" %
+                         (tuple(flow_f.shape) if isinstance(flow_f, torch.Tensor) else type(flow_f).__name__,))
+    nd = flow_f.dim() - 2
+    flow_f = _flow_operand("flow_f", flow_f.detach(), nd)
+    flow_b = _flow_operand("flow_b", flow_b.detach() if isinstance(flow_b, torch.Tensor) else flow_b, nd)
+    if flow_f.shape != flow_b.shape:
+        raise ValueError("flow_f and flow_b differ in shape: %s vs %s" % (tuple(flow_f.shape), tuple(flow_b.shape)))
+    if flow_f.device != flow_b.device:
+        raise ValueError("flow_f and flow_b are on different devices")
+    if (img0 is None) != (img1 is None):
+        raise ValueError("img0 and img1 go together: pass both or neither")
+    a1, a2 = (float(v) for v in alpha)
+    if not (0 <= a1 < float("inf") and 0 <= a2 < float("inf")):
+        raise ValueError("alpha must be two finite values >= 0, got %r" % (alpha,))
+    sp = tuple(int(s) for s in flow_f.shape[2:])
+    N = int(flow_f.shape[0])
+    mshape = (N,) + sp
+    dev = flow_f.device
+    images = img0 is not None
+    if images:
+        img0 = _flow_image("img0", img0.detach() if isinstance(img0, torch.Tensor) else img0, mshape, dev)
+        img1 = _flow_image("img1", img1.detach() if isinstance(img1, torch.Tensor) else img1, mshape, dev)
+    valid = _flow_mask("valid", valid, mshape, dev)
+    cmap = torch.empty(mshape, dtype=torch.uint8, device=dev) if return_maps else None
+    rmap = torch.empty(mshape, dtype=torch.float32, device=dev) if return_maps else None
+    if N == 0:
+        res = {k: torch.empty(0, dtype=torch.float64, device=dev) for k in _CONSISTENCY_KEYS}
+    else:
+        lib = _lib.lib()
+        nb = getattr(lib, "fs_flow_consistency%dd_ws_bytes" % nd)(N, nd, *sp)
+        if nb < 0:
+            _lib.check(int(-nb), "fs_flow_consistency%dd_ws_bytes" % nd)
+        ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(N, FLOW_CONSISTENCY_K, dtype=torch.float64, device=dev)
+        nbytes, flops = flow_consistency_cost(flow_f.shape, images, return_maps)
+        P = 1
+        for v in sp:
+            P *= v
+        fbs = flow_f.stride(0) if N > 1 else nd * P  # (a single flow's batch stride is never used)
+        bbs = flow_b.stride(0) if N > 1 else nd * P
+        args = (flow_f.data_ptr(), flow_b.data_ptr(), N, nd) + sp + (fbs, bbs, _ptr(img0), _ptr(img1), _ptr(valid),
+                                                                      a1, a2, _ptr(cmap), _ptr(rmap), ws.data_ptr(),
+                                                                      out.data_ptr(), _stream(flow_f))
+        with torch.cuda.device(dev):
+            _call("fs_flow_consistency%dd" % nd, *args, algo_bytes=nbytes, algo_flops=flops)
+        res = _consistency_stats(out, images)
+    if return_maps:
+        res.update(class_map=cmap, res_map=rmap, noc=cmap == FC_CONSISTENT)
+    return res
+
+
+def _consistency_stats(out, images):
+    """The per-pair statistics from the kernel's sums `out` [N, K] (fp64)."""
+    nan = torch.tensor(float("nan"), dtype=torch.float64, device=out.device)
+
+    def div(a, b):
+        return torch.where(b > 0, a / torch.where(b > 0, b, torch.ones_like(b)), nan)
+
+    n, nf, nout, nocc, nnoc = (out[:, k] for k in range(5))
+    nin = nocc + nnoc
+    res = {"fb_mean": div(out[:, 5], nin), "fb_rmse": torch.sqrt(div(out[:, 6], nin)),
+           "fb_max": torch.where(nin > 0, out[:, 7], nan), "fb_mean_noc": div(out[:, 8], nnoc),
+           "occ_frac": div(nocc, nin), "out_frac": div(nout, n),
+           "n_valid": n, "n_inside": nin, "n_noc": nnoc, "n_occ": nocc, "n_out": nout, "n_nonfinite": nf}
+    if images:
+        res.update(warp_l1=div(out[:, 9], nin), warp_l1_noc=div(out[:, 11], nnoc),
+                   warp_psnr=-10.0 * torch.log10(div(out[:, 10], nin)),
+                   warp_psnr_noc=-10.0 * torch.log10(div(out[:, 12], nnoc)))
+    else:
+        res.update({k: torch.full_like(n, float("nan")) for k in ("warp_l1", "warp_l1_noc", "warp_psnr", "warp_psnr_noc")})
+    return res
+
+
+# --------------------------------------------------------------------------------------------
 # Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
 # --------------------------------------------------------------------------------------------
 import numpy as _np
