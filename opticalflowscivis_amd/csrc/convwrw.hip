@@ -32,6 +32,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "common.hpp"
 
@@ -701,9 +702,9 @@ int launch_dma(const float* G, const float* Src, float* dW, const WP& w, hipStre
   return FS_OK;
 }
 
+#include "convwrw_s3.hpp"  // (first: convwrwwino4.hpp shares its w3_pack / w3_split)
 #include "convwrwwino.hpp"
 #include "convwrwwino4.hpp"
-#include "convwrw_s3.hpp"
 
 }  // namespace
 

@@ -23,6 +23,7 @@
 typedef __bf16 w3_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned w3_u32x4 __attribute__((ext_vector_type(4)));
 typedef float w3_f32x4 __attribute__((ext_vector_type(4)));
+typedef float w3_f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned w3_pack(float a, float b) {  // {bf16(a), bf16(b)}, round to nearest even
   typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -30,27 +31,39 @@ __device__ __forceinline__ unsigned w3_pack(float a, float b) {  // {bf16(a), bf
   return __builtin_bit_cast(unsigned, h);
 }
 
-// v[0..7] -> three bf16x8 pieces (element i of a piece is piece of v[i]); ab: measurement forms (FLOWSCI_WRW_S3_AB)
+// One piece of the split: the word {bf16 of ra, bf16 of rc}, and (ra, rc) become what the piece leaves of them.
+// OPAQUE: the packed word is hidden from the optimiser, which otherwise converts ra a second time (v_cvt_pk_bf16_f32 ra, 0)
+// to take the low half: 5 instead of 6 instructions (w3_split2<true>: convwrwwino4.hpp; the k4 kernels keep the
+// instruction stream they were validated and measured with).
+template <bool OPAQUE>
+__device__ __forceinline__ unsigned w3_peel(float& ra, float& rc) {
+  unsigned w = w3_pack(ra, rc);
+  if (OPAQUE) asm volatile("" : "+v"(w));
+  ra -= __uint_as_float(w << 16); rc -= __uint_as_float(w & 0xffff0000u);
+  asm volatile("" : "+v"(ra), "+v"(rc));  // (keeps the SLP vectoriser from pairing the subtractions: v_pk_add_f32 + moves)
+  return w;
+}
+
+// (ra, rc) -> word {bf16 of ra, bf16 of rc} of each of the three pieces; ab: measurement forms (FLOWSCI_WRW_S3_AB)
+template <bool OPAQUE = false>
+__device__ __forceinline__ void w3_split2(float ra, float rc, unsigned& w0, unsigned& w1, unsigned& w2, int ab) {
+#ifdef FS_ABLATION
+  if (ab & 1) {  // (measurement: no conversion -- the raw words as "pieces", wrong by design)
+    w0 = __float_as_uint(ra); w1 = __float_as_uint(rc); w2 = __float_as_uint(ra);
+    return;
+  }
+#endif
+  (void)ab;
+  w0 = w3_peel<OPAQUE>(ra, rc);
+  w1 = w3_peel<OPAQUE>(ra, rc);
+  w2 = w3_pack(ra, rc);
+}
+
+// v[0..7] -> three bf16x8 pieces (element i of a piece is piece of v[i])
 __device__ __forceinline__ void w3_split(const float (&v)[8], w3_bf16x8 (&h)[3], int ab) {
   unsigned w[3][4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float ra = v[2 * i], rc = v[2 * i + 1];
-#ifdef FS_ABLATION
-    if (ab & 1) {  // (measurement: no conversion -- the raw words as "pieces", wrong by design)
-      w[0][i] = __float_as_uint(ra); w[1][i] = __float_as_uint(rc); w[2][i] = __float_as_uint(ra);
-      continue;
-    }
-#endif
-    w[0][i] = w3_pack(ra, rc);
-    ra -= __uint_as_float(w[0][i] << 16); rc -= __uint_as_float(w[0][i] & 0xffff0000u);
-    asm volatile("" : "+v"(ra), "+v"(rc));  // (keeps the SLP vectoriser from pairing the subtractions: v_pk_add_f32 + moves)
-    w[1][i] = w3_pack(ra, rc);
-    ra -= __uint_as_float(w[1][i] << 16); rc -= __uint_as_float(w[1][i] & 0xffff0000u);
-    asm volatile("" : "+v"(ra), "+v"(rc));
-    w[2][i] = w3_pack(ra, rc);
-  }
-  (void)ab;
+  for (int i = 0; i < 4; ++i) w3_split2(v[2 * i], v[2 * i + 1], w[0][i], w[1][i], w[2][i], ab);
 #pragma unroll
   for (int pc = 0; pc < 3; ++pc) {
     const w3_u32x4 u = {w[pc][0], w[pc][1], w[pc][2], w[pc][3]};

@@ -1,11 +1,14 @@
-"""Micro-benchmark of fs_conv3d_wrw on the IFNet-3D layer shapes at 256^3 (GPU box only)."""
+"""Micro-benchmark of fs_conv3d_wrw on the IFNet-3D layer shapes at 256^3 (GPU box only).  Arguments: substrings of the
+row names to run (default: every row).  Each row names the kernel the library dispatches to and the arithmetic it runs:
+the product library's F(4,3) and k4 kernels multiply split-bf16 operands; the ablation build (FLOWSCI_HIP_LIBRARY) runs
+their fp32-MFMA forms under FLOWSCI_WRW_WINO4_NO_S3=1 / FLOWSCI_WRW_NO_S3=1."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from opticalflowscivis_amd import ops
 
 
-def t(fn, n=5):
+def t(fn, n=20):
     fn(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -15,13 +18,31 @@ def t(fn, n=5):
     return e0.elapsed_time(e1) / n
 
 
+KERNELS = {0: "brick", 1: "dma", 2: "wino F(2,3)", 3: "wino F(4,3)", 4: "k4 s3"}  # FS_WRW_KERNEL_*
+AB_LIB = bool(os.environ.get("FLOWSCI_HIP_LIBRARY"))  # (the product library reads no switch)
+
+
+def arithmetic(kid):
+    """INFERRED from the kernel id and the switches this process was started with -- the library is not asked, so a
+    misspelt switch prints the wrong label (the ablation library latches its switches at first use)."""
+    if kid == 3:
+        return "fp32 MFMA" if AB_LIB and os.environ.get("FLOWSCI_WRW_WINO4_NO_S3") else "split-bf16 x6"
+    if kid == 4:
+        return "split-bf16 x6"
+    return "fp32 MFMA"
+
+
 def case(name, cg, cs, k, s, out, B=2):
+    if len(sys.argv) > 1 and not any(a in name for a in sys.argv[1:]):
+        return
     inn = (out - 1) * s + k - 2
     g = torch.randn(B, cg, out, out, out, device="cuda")
     src = torch.randn(B, cs, inn, inn, inn, device="cuda")
     ms = t(lambda: ops.conv3d_wrw(g, src, k, s, 1))
     fl = 2.0 * cg * cs * k ** 3 * B * out ** 3
-    print("%-28s Cg=%3d Cs=%3d k%d s%d out=%3d^3: %.3f ms  %.1f TFLOP/s" % (name, cg, cs, k, s, out, ms, fl / ms / 1e9), flush=True)
+    kid = ops.conv3d_wrw_kernel_id(g.data_ptr(), src.data_ptr(), B, cg, cs, (out,) * 3, (inn,) * 3, k, s, 1)
+    print("%-28s Cg=%3d Cs=%3d k%d s%d out=%3d^3: %.3f ms  %.1f TFLOP/s  [%s, %s]"
+          % (name, cg, cs, k, s, out, ms, fl / ms / 1e9, KERNELS.get(kid, kid), arithmetic(kid)), flush=True)
 
 
 case("conv0a (11->32)", 32, 11, 4, 2, 128)
