@@ -49,8 +49,10 @@ enum {
  *   360  fs_triplet_gather, fs_series_stats / fs_series_stats_ws_bytes (training batches from a device-resident series).
  *   370  fs_census3d_dist_{fwd,bwd}, fs_flow_smooth3d_{fwd,bwd} (unsupervised flow-side loss terms of Flow-3D).
  *   380  fs_flow_consistency2d / fs_flow_consistency3d and their _ws_bytes queries (label-free flow quality:
- *        forward-backward residual, occlusion / outgoing / consistent classes, photometric error of the warp). */
-#define FS_ABI_VERSION 380
+ *        forward-backward residual, occlusion / outgoing / consistent classes, photometric error of the warp).
+ *   390  fs_series_encode / fs_series_encode_ws_bytes (padded fp32 planes back to a stored type: the inverse of the
+ *        gather's decode, for writing rebuilt series and flows). */
+#define FS_ABI_VERSION 390
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -794,6 +796,33 @@ int fs_triplet_gather(const void* base, int dtype, long long n_elems, int Ds, in
 long long fs_series_stats_ws_bytes(int T, long long frame_elems);
 int fs_series_stats(const void* base, int dtype, int T, long long frame_elems, double* ws, double* out,
                     fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * The way back: padded fp32 planes to a stored type -- the crop (`[..., :D, :H, :W]` of what a model returned for
+ * inputs padded to multiples of 32) and the conversion in one pass, so that a rebuilt series or its flows leave the
+ * device in the type they are kept in.
+ *   src: fp32 [N,C,Dp,Hp,Wp], contiguous.  dst: `dtype` (FS_SERIES_*) [N,C,D,H,W], contiguous, = the corner
+ *   [0:D, 0:H, 0:W] of every plane (Dp = D = 1 for 2-D).
+ *   Per element y = x * span, then y = y + lo: two separately rounded fp32 operations (no FMA), the inverse of the
+ *   gather's (v - lo) * inv up to rounding.  A non-finite y is stored as 0 and counted as non-finite (neither low nor
+ *   high).  U8 / U16: low when y < 0, high when y > 255 / 65535; clamped, rounded to nearest even, converted.  F16:
+ *   low / high when y < -65504 / y > 65504; saturated to +-65504, else fp32 -> half with round to nearest even.
+ *   F32: y itself (nothing is low or high).
+ *   stats (nullable, together with ws): fp64 [N,5] = {min y, max y over the finite y before clamping (+inf / -inf if
+ *   none), n_low, n_high, n_nonfinite} over all C planes of item n.  Partials per workgroup in `ws`
+ *   (fs_series_encode_ws_bytes bytes, 8-byte aligned), combined by a second launch in a fixed order: no atomics; which
+ *   elements a lane reduces depends on the shape alone, so the stats do not depend on pointer alignment.  With
+ *   ws == stats == NULL one launch, no reduction.
+ *   A lane owns 4 consecutive outputs of a row when W % 4 == 0 and Wp % 4 == 0 (one 16-byte load and one 4 / 8 /
+ *   16-byte store when src is 16-byte aligned and dst aligned to 4 elements), one element otherwise.
+ *   FS_ERR_NULLPTR: src or dst NULL, exactly one of ws / stats NULL.  FS_ERR_SHAPE: an extent < 1, D > Dp, H > Hp,
+ *   W > Wp, N > 2^20, more than 2^31-1 padded elements per item or 2^40 in all.  FS_ERR_ARG: an unknown dtype, dst not
+ *   aligned to its element, src to 4 bytes, ws / stats to 8.  The _ws_bytes query launches nothing and returns the
+ *   byte count or -(FS_ERR_*).
+ */
+long long fs_series_encode_ws_bytes(int N, int C, int D, int H, int W);
+int fs_series_encode(const float* src, int N, int C, int Dp, int Hp, int Wp, void* dst, int dtype, int D, int H, int W,
+                     float lo, float span, double* ws, double* stats, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Census distance on volumes: the arithmetic of a8 (UPFlow/utils/loss.py:59-71) without the grey conversion, a volume

@@ -33,7 +33,7 @@ def switches():
     return {"library": "ablation build: " + LIB_PATH if ABLATION else "product",
             "env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("FLOWSCI_")}}
 
-ABI_VERSION = 380  # FS_ABI_VERSION of the include/flowsci_hip.h the SIGNATURES below were written against
+ABI_VERSION = 390  # FS_ABI_VERSION of the include/flowsci_hip.h the SIGNATURES below were written against
 
 _f32p = ctypes.c_void_p  # device pointers travel as integers
 _int = ctypes.c_int
@@ -149,6 +149,8 @@ SIGNATURES = {
     "fs_triplet_gather": [_f32p, _int, _i64, _int, _int, _int, _f32p, _int, _int, _int, _int, _f32p, _stream],
     "fs_series_stats_ws_bytes": [_int, _i64],
     "fs_series_stats": [_f32p, _int, _int, _i64, _f32p, _f32p, _stream],
+    "fs_series_encode_ws_bytes": [_int] * 5,
+    "fs_series_encode": [_f32p] + [_int] * 5 + [_f32p] + [_int] * 4 + [_float, _float, _f32p, _f32p, _stream],
     "fs_census3d_dist_fwd": [_f32p] * 3 + [_int] * 5 + [_stream],
     "fs_census3d_dist_bwd": [_f32p] * 5 + [_int] * 5 + [_stream],
     "fs_flow_smooth3d_fwd": [_f32p] * 4 + [_int] * 5 + [_float] * 3 + [_stream],
@@ -159,7 +161,7 @@ _RESTYPES = {"fs_error_string": ctypes.c_char_p, "fs_conv3d_fwd_ws_floats": ctyp
              "fs_frame_metrics2d_ws_bytes": ctypes.c_longlong, "fs_frame_metrics3d_ws_bytes": ctypes.c_longlong,
              "fs_flow_metrics2d_ws_bytes": ctypes.c_longlong, "fs_flow_metrics3d_ws_bytes": ctypes.c_longlong,
              "fs_flow_consistency2d_ws_bytes": ctypes.c_longlong, "fs_flow_consistency3d_ws_bytes": ctypes.c_longlong,
-             "fs_series_stats_ws_bytes": ctypes.c_longlong,
+             "fs_series_stats_ws_bytes": ctypes.c_longlong, "fs_series_encode_ws_bytes": ctypes.c_longlong,
              "fs_conv3d_tr_ws_floats": ctypes.c_longlong, "fs_conv3d_fwd_dprelu_part_floats": ctypes.c_longlong,
              "fs_conv3d_fwd_dprelu_part_floats_k3": ctypes.c_longlong}
 

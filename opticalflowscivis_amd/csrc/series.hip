@@ -23,6 +23,16 @@
 //
 // fs_series_stats: per stored frame the minimum and maximum over the finite elements and the count of non-finite
 // ones; per-workgroup partials in `ws`, a second launch combines them in a fixed order (no atomics).
+//
+// fs_series_encode: the way back -- the corner [0:D, 0:H, 0:W] of padded fp32 planes [N,C,Dp,Hp,Wp] written as a
+// contiguous [N,C,D,H,W] array of a stored type (the crop and the conversion in one pass).  Per element y = x * span,
+// then y = y + lo (two separately rounded fp32 operations); a non-finite y is stored as 0; u8 / u16 clamp to the type
+// and round to nearest even, f16 saturates at +-65504 and converts with round to nearest even, f32 stores y.
+// Optionally per item {min y, max y over the finite y before clamping, n below, n above, n non-finite}: partials per
+// workgroup, a second launch in fixed order.  The same stream layout as the gather: with W % 4 == 0 and Wp % 4 == 0 a
+// lane owns 4 consecutive outputs of a row (one 16-byte load and one 4 / 8 / 16-byte store when both pointers allow
+// it, 4 element accesses otherwise -- which lane reduces which elements is a function of the shape alone), else one
+// element per lane.
 #include "common.hpp"
 
 namespace {
@@ -251,6 +261,185 @@ void launch_stats(const void* base, double* ws, double* out, int T, long long F,
   hipLaunchKernelGGL(series_stats_final_kernel, dim3((unsigned)T), dim3(NT), 0, s, ws, G, out);
 }
 
+// ---------------------------------------------------------------------------------------------- fs_series_encode
+struct EncAcc {
+  float mn, mx;
+  unsigned long long low, high, bad;
+};
+
+// y -> the stored value; counts what clamping and the non-finite rule changed.
+struct EU8 {
+  typedef unsigned char S;
+  static __device__ __forceinline__ S enc(float y, EncAcc& a) {
+    a.low += y < 0.f; a.high += y > 255.f;
+    return (S)(int)rintf(fminf(fmaxf(y, 0.f), 255.f));
+  }
+};
+struct EU16 {
+  typedef unsigned short S;
+  static __device__ __forceinline__ S enc(float y, EncAcc& a) {
+    a.low += y < 0.f; a.high += y > 65535.f;
+    return (S)(int)rintf(fminf(fmaxf(y, 0.f), 65535.f));
+  }
+};
+struct EF16 {
+  typedef unsigned short S;
+  static __device__ __forceinline__ S enc(float y, EncAcc& a) {
+    a.low += y < -65504.f; a.high += y > 65504.f;
+    const _Float16 h = (_Float16)fminf(fmaxf(y, -65504.f), 65504.f);  // round to nearest even
+    S s;
+    __builtin_memcpy(&s, &h, 2);
+    return s;
+  }
+};
+struct EF32 {
+  typedef float S;
+  static __device__ __forceinline__ S enc(float y, EncAcc&) { return y; }
+};
+
+struct EP {
+  unsigned Q;        // work items per item of the batch: C*D*H*W / V
+  int C, Dp, Hp, Wp, D, H, W;
+  int G;             // workgroups per item
+  int vec;           // src 16-byte aligned and dst aligned to 4 elements: vector accesses (V == 4 only)
+  float lo, span;
+};
+
+template <class E, int V, bool STATS>
+__global__ __launch_bounds__(NT) void series_encode_kernel(const float* __restrict__ src,
+                                                           typename E::S* __restrict__ dst, double* __restrict__ ws,
+                                                           EP g) {
+#pragma clang fp contract(off)
+  typedef typename E::S S;
+  const int n = blockIdx.x / g.G, blk = blockIdx.x - n * g.G;
+  const unsigned GW = (unsigned)(g.W / V);
+  const unsigned DH = (unsigned)g.D * (unsigned)g.H;
+  const size_t rows = (size_t)g.C * DH;  // output rows per item
+  const float* sb = src + (size_t)n * g.C * g.Dp * g.Hp * g.Wp;
+  S* db = dst + (size_t)n * rows * g.W;
+  EncAcc a = {HUGE_VALF, -HUGE_VALF, 0ull, 0ull, 0ull};
+  for (unsigned q = (unsigned)blk * NT + threadIdx.x; q < g.Q; q += (unsigned)g.G * NT) {
+    const unsigned row = q / GW;
+    const unsigned x = (q - row * GW) * V;
+    const unsigned c = row / DH, r = row - c * DH;
+    const unsigned z = r / (unsigned)g.H, y0 = r - z * (unsigned)g.H;
+    const float* sp = sb + (((size_t)c * g.Dp + z) * g.Hp + y0) * g.Wp + x;
+    S* dp = db + (size_t)row * g.W + x;
+    float v[V];
+    if (V == 4 && g.vec) {
+      const float4 f = *reinterpret_cast<const float4*>(sp);
+      v[0] = f.x; v[V > 1 ? 1 : 0] = f.y; v[V > 2 ? 2 : 0] = f.z; v[V > 3 ? 3 : 0] = f.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < V; ++i) v[i] = sp[i];
+    }
+    Pack<S, V> pk;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      float y = v[i] * g.span;
+      y = y + g.lo;
+      if (finite32(y)) {
+        a.mn = fminf(a.mn, y); a.mx = fmaxf(a.mx, y);
+        pk.s[i] = E::enc(y, a);
+      } else {
+        ++a.bad;
+        pk.s[i] = (S)0;
+      }
+    }
+    if (V == 4 && g.vec) {
+      *reinterpret_cast<Pack<S, V>*>(dp) = pk;
+    } else {
+#pragma unroll
+      for (int i = 0; i < V; ++i) dp[i] = pk.s[i];
+    }
+  }
+  if (!STATS) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a.mn = fminf(a.mn, __shfl_xor(a.mn, o, 64));
+    a.mx = fmaxf(a.mx, __shfl_xor(a.mx, o, 64));
+    a.low += __shfl_xor(a.low, o, 64);
+    a.high += __shfl_xor(a.high, o, 64);
+    a.bad += __shfl_xor(a.bad, o, 64);
+  }
+  __shared__ float rmn[NT / 64], rmx[NT / 64];
+  __shared__ unsigned long long rcnt[3][NT / 64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) { rmn[wv] = a.mn; rmx[wv] = a.mx; rcnt[0][wv] = a.low; rcnt[1][wv] = a.high; rcnt[2][wv] = a.bad; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* w = ws + ((size_t)n * g.G + blk) * 5;
+    w[0] = (double)fminf(fminf(rmn[0], rmn[1]), fminf(rmn[2], rmn[3]));
+    w[1] = (double)fmaxf(fmaxf(rmx[0], rmx[1]), fmaxf(rmx[2], rmx[3]));
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      w[2 + k] = (double)rcnt[k][0] + (double)rcnt[k][1] + (double)rcnt[k][2] + (double)rcnt[k][3];
+  }
+}
+
+// Second stage: one workgroup per item combines its G partials -> out[n] = {min, max, n_low, n_high, n_nonfinite}.
+__global__ __launch_bounds__(NT) void series_encode_final_kernel(const double* __restrict__ ws, int G,
+                                                                 double* __restrict__ out) {
+  __shared__ double red[5][NT];
+  const double* w = ws + (size_t)blockIdx.x * G * 5;
+  double v[5] = {HUGE_VAL, -HUGE_VAL, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < G; i += NT) {
+    v[0] = fmin(v[0], w[5 * i]);
+    v[1] = fmax(v[1], w[5 * i + 1]);
+#pragma unroll
+    for (int k = 2; k < 5; ++k) v[k] += w[5 * i + k];  // integers below 2^53: exact in any order
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) red[k][threadIdx.x] = v[k];
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red[0][threadIdx.x] = fmin(red[0][threadIdx.x], red[0][threadIdx.x + s]);
+      red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + s]);
+#pragma unroll
+      for (int k = 2; k < 5; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 5) out[(size_t)blockIdx.x * 5 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// Workgroups per item: a function of the OUTPUT shape alone (the workspace query does not know the padded extents).
+int encode_plan(int N, int C, int D, int H, int W, int& G) {
+  if (N < 1 || C < 1 || D < 1 || H < 1 || W < 1 || N > (1 << 20)) return FS_ERR_SHAPE;
+  const long long per = (long long)C * D;  // < 2^62
+  if (per > 0x7fffffffLL || per * H > 0x7fffffffLL || per * H * W > 0x7fffffffLL) return FS_ERR_SHAPE;
+  const long long e = per * H * W;
+  if (e * N > (1LL << 40)) return FS_ERR_SHAPE;
+  long long g = (kTargetBlocks + N - 1) / N;
+  const long long gmax = (e + NT * 4 - 1) / (NT * 4);
+  if (g > gmax) g = gmax;
+  if (g < 1) g = 1;
+  G = (int)g;
+  return FS_OK;
+}
+
+template <class E>
+void launch_encode(const float* src, void* dst, double* ws, double* stats, EP g, int N, hipStream_t s) {
+  typedef typename E::S S;
+  const bool v4 = g.W % 4 == 0 && g.Wp % 4 == 0;
+  g.Q = (unsigned)((long long)g.C * g.D * g.H * g.W / (v4 ? 4 : 1));
+  g.vec = v4 && aligned(src, 16) && aligned(dst, 4 * sizeof(S));
+  const dim3 grid((unsigned)(N * g.G)), blk(NT);
+  if (ws) {
+    if (v4)
+      hipLaunchKernelGGL((series_encode_kernel<E, 4, true>), grid, blk, 0, s, src, (S*)dst, ws, g);
+    else
+      hipLaunchKernelGGL((series_encode_kernel<E, 1, true>), grid, blk, 0, s, src, (S*)dst, ws, g);
+    hipLaunchKernelGGL(series_encode_final_kernel, dim3((unsigned)N), dim3(NT), 0, s, ws, g.G, stats);
+  } else {
+    if (v4)
+      hipLaunchKernelGGL((series_encode_kernel<E, 4, false>), grid, blk, 0, s, src, (S*)dst, ws, g);
+    else
+      hipLaunchKernelGGL((series_encode_kernel<E, 1, false>), grid, blk, 0, s, src, (S*)dst, ws, g);
+  }
+}
+
 }  // namespace
 
 extern "C" int fs_triplet_gather(const void* base, int dtype, long long n_elems, int Ds, int Hs, int Ws,
@@ -306,6 +495,41 @@ extern "C" int fs_series_stats(const void* base, int dtype, int T, long long fra
     case FS_SERIES_U16: launch_stats<U16>(base, ws, out, T, frame_elems, G, s); break;
     case FS_SERIES_F16: launch_stats<F16>(base, ws, out, T, frame_elems, G, s); break;
     default: launch_stats<F32>(base, ws, out, T, frame_elems, G, s); break;
+  }
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+extern "C" long long fs_series_encode_ws_bytes(int N, int C, int D, int H, int W) {
+  int G = 0;
+  const int rc = encode_plan(N, C, D, H, W, G);
+  if (rc != FS_OK) return -rc;
+  return (long long)N * G * 5 * (long long)sizeof(double);
+}
+
+extern "C" int fs_series_encode(const float* src, int N, int C, int Dp, int Hp, int Wp, void* dst, int dtype, int D,
+                                int H, int W, float lo, float span, double* ws, double* stats, fs_stream_t stream) {
+  FS_ENTER();
+  FS_REQUIRE_PTR(src); FS_REQUIRE_PTR(dst);
+  if ((ws == nullptr) != (stats == nullptr)) return FS_ERR_NULLPTR;
+  EP g;
+  int rc = encode_plan(N, C, D, H, W, g.G);
+  if (rc != FS_OK) return rc;
+  if (Dp < 1 || Hp < 1 || Wp < 1 || D > Dp || H > Hp || W > Wp) return FS_ERR_SHAPE;
+  int Gp = 0;  // the padded planes obey the same limits
+  rc = encode_plan(N, C, Dp, Hp, Wp, Gp);
+  if (rc != FS_OK) return rc;
+  const int es = elem_size(dtype);
+  if (es == 0) return FS_ERR_ARG;
+  if (!aligned(src, 4) || !aligned(dst, (size_t)es) || !aligned(ws, 8) || !aligned(stats, 8)) return FS_ERR_ARG;
+  g.C = C; g.Dp = Dp; g.Hp = Hp; g.Wp = Wp; g.D = D; g.H = H; g.W = W;
+  g.lo = lo; g.span = span;
+  const hipStream_t s = (hipStream_t)stream;
+  switch (dtype) {
+    case FS_SERIES_U8: launch_encode<EU8>(src, dst, ws, stats, g, N, s); break;
+    case FS_SERIES_U16: launch_encode<EU16>(src, dst, ws, stats, g, N, s); break;
+    case FS_SERIES_F16: launch_encode<EF16>(src, dst, ws, stats, g, N, s); break;
+    default: launch_encode<EF32>(src, dst, ws, stats, g, N, s); break;
   }
   FS_LAUNCH_CHECK();
   return FS_OK;

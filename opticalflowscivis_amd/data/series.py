@@ -5,6 +5,8 @@ Three layers:
   * `load_series`: .npy (memory-mapped), .npz, .pkl (one pickled numpy array, the reference's own format);
   * `TripletPlan`: the index arithmetic -- which frames, which crop, which mirrors, which normalisation -- as
     64-byte records (ops.TRIPLET_JOB), pure numpy, no GPU;
+  * `SeriesWriter` / `encode_numpy`: the way back -- an .npy file written frame by frame in a stored type
+    (reconstruct.reconstruct_series), and the rule ops.series_encode applies, in numpy;
   * `FileTriplets` (a Dataset: the records applied with numpy, for the host loaders) and `DeviceSeriesLoader` (the
     stored array uploaded once in its stored type, a batch = one ops.triplet_gather launch over its records).
 
@@ -248,6 +250,73 @@ def gather_numpy(arr, rec, frame, crop):
             v[~np.isfinite(v)] = 0.0
         out[c] = (v - np.float32(rec["lo"])) * np.float32(rec["inv"])
     return out.reshape((3,) + tuple(crop))
+
+
+ENCODE_LIMITS = {"uint8": (0.0, 255.0), "uint16": (0.0, 65535.0), "float16": (-65504.0, 65504.0)}
+
+
+def encode_numpy(x, dtype, lo=0.0, span=1.0):
+    """fp32 `x` as `dtype` by the rule of ops.series_encode, bit for bit: y = x * span, then y + lo (two rounded fp32
+    operations); a non-finite y is stored as 0; uint8 / uint16 clamp to the type and round to nearest even, float16
+    saturates at +-65504 and rounds to nearest even, float32 keeps y.  With lo = 0, span = 1 this is also the
+    conversion a stored keyframe gets when the output type differs from its own."""
+    dtype = np.dtype(dtype)
+    if dtype not in [np.dtype(t) for t in STORED_DTYPES]:
+        raise ValueError("encode to uint8, uint16, float16 or float32, got %s" % dtype)
+    with np.errstate(all="ignore"):
+        y = np.asarray(x, np.float32) * np.float32(span)
+        y = y + np.float32(lo)
+        y = np.where(np.isfinite(y), y, np.float32(0))
+        if dtype.name in ENCODE_LIMITS:
+            a, b = ENCODE_LIMITS[dtype.name]
+            y = np.clip(y, np.float32(a), np.float32(b))
+            if dtype.kind == "u":
+                y = np.rint(y)
+        return y.astype(dtype)
+
+
+class SeriesWriter:
+    """An .npy file of `shape` and `dtype` written frame by frame (numpy.lib.format.open_memmap: the header first, the
+    frames in place, nothing held in memory).  `source`: the file the series was read from -- writing over it is
+    refused (the input is a memory map of that file).  An existing file is refused unless `overwrite`.  `close()`
+    flushes; also a context manager."""
+
+    def __init__(self, path, shape, dtype, overwrite=False, source=None):
+        if os.path.splitext(path)[1].lower() != ".npy":
+            raise ValueError("the output is written as .npy, got %r" % path)
+        if source is not None and os.path.realpath(path) == os.path.realpath(source):
+            raise ValueError("%s is the input itself: write the result somewhere else" % path)
+        if os.path.exists(path) and not overwrite:
+            raise FileExistsError("%s exists: pass overwrite=True / --overwrite to replace it" % path)
+        dtype = np.dtype(dtype)
+        if dtype not in [np.dtype(t) for t in STORED_DTYPES]:
+            raise ValueError("write uint8, uint16, float16 or float32, got %s" % dtype)
+        d = os.path.dirname(os.path.abspath(path))
+        os.makedirs(d, exist_ok=True)
+        self.path, self.shape, self.dtype = path, tuple(int(s) for s in shape), dtype
+        self._mm = np.lib.format.open_memmap(path, mode="w+", dtype=dtype, shape=self.shape)
+
+    def write(self, index, frame):
+        """Frame `index` = `frame` (any shape with the frame's element count, the file's dtype)."""
+        if self._mm is None:
+            raise ValueError("%s is closed" % self.path)
+        if not 0 <= index < self.shape[0]:
+            raise IndexError("frame %d of %d" % (index, self.shape[0]))
+        frame = np.asarray(frame)
+        if frame.dtype != self.dtype:
+            raise ValueError("frame %d is %s, the file stores %s" % (index, frame.dtype, self.dtype))
+        self._mm[index] = frame.reshape(self.shape[1:])
+
+    def close(self):
+        if self._mm is not None:
+            self._mm.flush()
+            self._mm = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class FileTriplets(Dataset):

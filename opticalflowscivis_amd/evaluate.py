@@ -32,6 +32,42 @@ def _mid(model, a, b):
     return m[2] if isinstance(m, list) else m
 
 
+def bisection_groups(T, factor, batch, device):
+    """The model calls of bisect_keyframes on a [T, ...] sequence, in order: [(idx, half, step, positions)] with idx
+    the device tensor of the left parents' indices of one group of at most `batch` pairs and positions = the list
+    idx + half.  Every index of every level goes up in ONE copy from pinned memory that does not block the host: a
+    `torch.tensor(list, device=...)` per group is a pageable copy, and PyTorch synchronises the stream behind it --
+    the host would wait for every model call before it could launch the next."""
+    groups, flat = [], []
+    step = factor
+    while step > 1:
+        half = step // 2
+        left = list(range(0, T - 1, step))
+        for i in range(0, len(left), batch):
+            g = left[i:i + batch]
+            groups.append((len(flat), len(g), half, step, [l + half for l in g]))
+            flat += g
+        step = half
+    if not flat:
+        return []
+    dev = torch.tensor(flat).pin_memory().to(device, non_blocking=True)
+    return [(dev[a:a + n], half, step, pos) for a, n, half, step, pos in groups]
+
+
+def bisect_keyframes(seq, factor, batch, mid, groups=None):
+    """The keyframe-level loop of interpolate_sequence (shared with reconstruct.reconstruct_series, which runs it on
+    one chunk of keyframes at a time): seq [T,1,*padded], T = (K-1)*factor + 1, holds the keyframes at seq[::factor];
+    every other frame is filled in place, level by level (step = factor, factor/2, ..., 2), the midpoints of one level
+    in groups of `batch` pairs from the left: seq[i + step/2] = mid(seq[i], seq[i + step], positions), positions = the
+    list of the indices i + step/2 of the group.  groups: bisection_groups(T, factor, batch, device) when the caller
+    has them already (the same T again and again); nothing here makes the host wait for the device."""
+    if groups is None:
+        groups = bisection_groups(seq.shape[0], factor, batch, seq.device)
+    with torch.no_grad():
+        for idx, half, step, pos in groups:
+            seq[idx + half] = mid(seq[idx], seq[idx + step], pos)
+
+
 def interpolate_sequence(model, frames, factor, batch=1):
     """Rebuild [T, *spatial] `frames` from its keyframes frames[::factor]: recursive bisection with model.inference
     (flow{2,3}d/inference_img.py), inputs padded to multiples of 32 and the results cropped as there.  Every midpoint of
@@ -49,15 +85,7 @@ def interpolate_sequence(model, frames, factor, batch=1):
     padded = _pad32(keys.to(torch.float32).reshape((K, 1) + sp), nd)
     seq = padded.new_zeros((T,) + tuple(padded.shape[1:]))
     seq[::factor] = padded
-    step = factor
-    with torch.no_grad():
-        while step > 1:
-            half = step // 2
-            left = list(range(0, T - 1, step))
-            for i in range(0, len(left), batch):
-                idx = torch.tensor(left[i:i + batch], device=seq.device)
-                seq[idx + half] = _mid(model, seq[idx], seq[idx + step])
-            step = half
+    bisect_keyframes(seq, factor, batch, lambda a, b, pos: _mid(model, a, b))
     out = seq[(slice(None), 0) + tuple(slice(0, s) for s in sp)].clone()
     out[::factor] = frames[::factor]  # (bit for bit, also for inputs that are not fp32)
     return out

@@ -2811,3 +2811,66 @@ def series_stats(stored):
         _call("fs_series_stats", stored.data_ptr(), SERIES_DTYPES[stored.dtype], T, F, ws.data_ptr(), out.data_ptr(),
               _stream(stored), algo_bytes=stored.numel() * stored.element_size())
     return out
+
+
+def series_encode_cost(shape_out, itemsize):
+    """(HBM bytes, flops) one series_encode needs by the algorithm: every kept element read once as fp32 and written
+    once in the stored type (the padding is never touched); a multiply and an add per element."""
+    n = 1
+    for s in shape_out:
+        n *= int(s)
+    return n * (4 + int(itemsize)), 2 * n
+
+
+def _series_dtype(dtype):
+    if isinstance(dtype, torch.dtype):
+        t = dtype
+    else:
+        t = getattr(torch, _np.dtype(dtype).name, None)
+    if t not in SERIES_DTYPES:
+        raise ValueError("dtype must be uint8, uint16, float16 or float32, got %r" % (dtype,))
+    return t
+
+
+def series_encode(x, dtype, spatial, lo=0.0, span=1.0, out=None, stats=True):
+    """The inverse of the gather's decode, one launch (fs_series_encode): the corner [:D,:H,:W] ([:H,:W]) of the padded
+    fp32 planes x [N,C,*padded] written as a contiguous `dtype` [N,C,*spatial] tensor, y = x * span + lo (two rounded
+    fp32 operations); uint8 / uint16 clamp and round to nearest even, float16 saturates at +-65504, a non-finite y is
+    stored as 0.  Returns (stored tensor, stats): stats an fp64 [N,5] tensor {min y, max y over the finite y before
+    clamping, n_low, n_high, n_nonfinite} per item (a second, fixed-order launch; nothing synchronises), or None with
+    stats=False.  out: a contiguous `dtype` [N,C,*spatial] tensor on x's device to write into, e.g. a view into a
+    larger staging buffer."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError("x must be a tensor")
+    if not x.is_cuda:
+        raise ValueError("x must live on a GPU (the HIP hot path has no CPU fallback); got %s" % x.device)
+    spatial = tuple(int(s) for s in spatial)
+    nd = len(spatial)
+    if nd not in (2, 3) or x.dtype != torch.float32 or x.dim() != nd + 2:
+        raise ValueError("x must be float32 [N,C,*padded] with %d padded extents for spatial %s, got %s %s" %
+                         (nd, spatial, x.dtype, tuple(x.shape)))
+    tdt = _series_dtype(dtype)
+    x = x.contiguous()
+    N, C = int(x.shape[0]), int(x.shape[1])
+    padded = tuple(int(s) for s in x.shape[2:])
+    if N < 1 or C < 1 or any(s < 1 or s > p for s, p in zip(spatial, padded)):
+        raise ValueError("spatial %s does not fit the planes of x %s" % (spatial, tuple(x.shape)))
+    shape = (N, C) + spatial
+    if out is None:
+        out = torch.empty(shape, dtype=tdt, device=x.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != tdt or tuple(out.shape) != shape or
+          not out.is_contiguous() or out.device != x.device):
+        raise ValueError("out must be a contiguous %s %s tensor on x's device" % (tdt, shape))
+    p3, s3 = (1,) * (3 - nd) + padded, (1,) * (3 - nd) + spatial
+    ws = st = None
+    if stats:
+        nb = _lib.lib().fs_series_encode_ws_bytes(N, C, *s3)
+        if nb < 0:
+            _lib.check(int(-nb), "fs_series_encode_ws_bytes")
+        ws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
+        st = torch.empty(N, 5, dtype=torch.float64, device=x.device)
+    nbytes, flops = series_encode_cost(shape, out.element_size())
+    with torch.cuda.device(x.device):
+        _call("fs_series_encode", x.data_ptr(), N, C, *p3, out.data_ptr(), SERIES_DTYPES[tdt], *s3, float(lo),
+              float(span), _ptr(ws), _ptr(st), _stream(x), algo_bytes=nbytes, algo_flops=flops)
+    return out, st

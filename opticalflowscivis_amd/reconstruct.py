@@ -1,0 +1,415 @@
+"""Temporal up-sampling of a stored series, file to file (the reference's third task, Flow-3D/inference_img.py and
+error.py:374-436, for a whole series instead of one pair): every stored frame is a keyframe, the 2**exp - 1 frames
+between two neighbours are rebuilt by the model with recursive bisection and written -- with the keyframes -- to an
+.npy file in the stored type (or another of uint8 / uint16 / float16 / float32), optionally with the flows that
+produced them.  Shared by the flow2d / flow3d `reconstruct` entry points:
+
+    python -m opticalflowscivis_amd.flow3d.reconstruct --series sim.npy --exp 2 --out sim_x4.npy --flows flows.npy
+    python -m opticalflowscivis_amd.flow2d.reconstruct --series img.npy --dtype float32 --range 0 4095 --out up.npy
+
+The series streams through the device one chunk of keyframe pairs at a time (`reconstruct_series`): device memory is a
+function of chunk, exp, batch and the frame size, never of the number of frames.  Per chunk: its new keyframes go up in
+the stored type through pinned memory on a side stream (the keyframe shared with the previous chunk stays on the
+device); ops.triplet_gather decodes them as training does, (v - lo) * inv; evaluate.bisect_keyframes fills the frames
+in between exactly as evaluate.interpolate_sequence does on that sub-series; ONE ops.series_encode launch crops,
+de-normalises (x * span + lo) and converts the new frames into a device staging buffer in the output type; the side
+stream copies that buffer into one of two pinned buffers; the host places the previous chunk's frames into the output
+memory map while this chunk computes.  Inside the loop the host waits on copy events only: the bisection's indices and
+the decode records go up in front of it (a pageable upload per model call would synchronise the compute stream and
+with it serialise placement and inference), so the host runs ahead of the device and places while the model runs.
+
+Keyframe positions of the output receive the stored values themselves (bit for bit when the output type is the
+stored one, else converted on the host by the encode rule with lo = 0, span = 1: data.series.encode_numpy).
+
+Out of scope: factors that are not powers of two, the per-frame normalisation ('frame': one encode launch takes one
+(lo, span) pair) and UPFlow (it estimates flow, it does not interpolate)."""
+import argparse
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import ops
+from .data.series import STORED_DTYPES, SeriesWriter, encode_numpy, load_series, series_layout
+from .evaluate import _pad32, bisect_keyframes, bisection_groups
+
+NORMALIZE = ("global", "none")
+STAT_NAMES = ("min", "max", "n_low", "n_high", "n_nonfinite")
+
+
+def plan_chunks(K, exp, chunk):
+    """The chunks of a series of K keyframes at factor 2**exp, `chunk` keyframe pairs each (the last one may be
+    shorter): [{'keys': (k0, k1) -- keyframes k0..k1 inclusive, 'frames': output indices of the frames the chunk
+    produces, ascending, 'parents': per produced frame the output indices of the two frames it is the midpoint of}].
+    Pure index arithmetic: frame base + p (p not a multiple of the factor) is produced at the bisection level
+    h = lowest set bit of p from the frames base + p - h and base + p + h."""
+    if K < 2:
+        raise ValueError("need at least two stored frames, got %d" % K)
+    if exp < 1:
+        raise ValueError("exp must be >= 1 (factor 2**exp), got %d" % exp)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1, got %d" % chunk)
+    factor = 2 ** exp
+    out = []
+    for k0 in range(0, K - 1, chunk):
+        k1 = min(k0 + chunk, K - 1)
+        base = k0 * factor
+        frames, parents = [], []
+        for p in range(1, (k1 - k0) * factor):
+            if p % factor:
+                h = p & -p
+                frames.append(base + p)
+                parents.append((base + p - h, base + p + h))
+        out.append({"keys": (k0, k1), "frames": frames, "parents": parents})
+    return out
+
+
+def normalisation(normalize, lo_hi):
+    """(lo, inv, span) as fp32 numbers: lo and inv exactly as data.series.TripletPlan.records computes them from the
+    range (lo, hi) -- a bound that is not finite reads as 0, inv = 1 / (hi - lo) in fp32 or 1 when that difference is
+    not positive -- and span = hi - lo (fp32) or 1 likewise.  'none': 0, 1, 1."""
+    if normalize == "none":
+        return np.float32(0), np.float32(1), np.float32(1)
+    lo, hi = (np.float32(v) if np.isfinite(v) else np.float32(0) for v in (np.float64(lo_hi[0]), np.float64(lo_hi[1])))
+    d = np.float32(hi - lo)
+    if d > 0:
+        return lo, np.float32(1) / d, d
+    return lo, np.float32(1), np.float32(1)
+
+
+def _torch_dtype(dt):
+    return getattr(torch, np.dtype(dt).name)
+
+
+class _Slot:
+    """One of the two pinned staging buffers: the chunk's new keyframes on their way up, its frames, flows and stats
+    rows on their way down; `copied` is recorded on the side stream behind the downward copies."""
+
+    def __init__(self, key_bytes, frame_bytes, flow_bytes, rows):
+        pin = lambda n: torch.empty(max(int(n), 1), dtype=torch.uint8).pin_memory()
+        self.keys, self.frames, self.flows = pin(key_bytes), pin(frame_bytes), pin(flow_bytes)
+        self.stats = torch.empty(max(rows, 1), 5, dtype=torch.float64).pin_memory()
+        self.copied = torch.cuda.Event()
+        self.d2h = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        self.pending = None  # the chunk whose results the buffer holds until the host has placed them
+        self.uses = 0
+
+
+def reconstruct_series(model, stored, exp, writer, batch=1, chunk=1, normalize="global", norm_range=None,
+                       flow_writer=None, nd=None):
+    """Up-sample `stored` (the load_series array: [K,*sp] or [K,1,*sp], any of STORED_DTYPES, memory-mapped or not) by
+    2**exp in time into `writer` (a SeriesWriter of [(K-1)*2**exp + 1, *sp] or [.., 1, *sp]; its dtype is the output
+    type) and, with `flow_writer` (float16 / float32 [M, 2*nd, *sp], M = (K-1)*(2**exp - 1)), the final flows of every
+    produced frame toward its two parents (displacements, as flow_eval.rife_flows returns them), in output-frame order.
+
+    normalize 'global': the model sees (v - lo) * inv with (lo, hi) = `norm_range` or the range of the finite stored
+    elements (ops.series_stats over the uploaded keyframes, one pass in front); 'none': the values as stored.  batch:
+    midpoints per model call; chunk: keyframe pairs per chunk.  The bisection inside a chunk is
+    evaluate.interpolate_sequence's on that sub-series, so at batch = 1 the frames do not depend on `chunk`.
+    nd: 2 or 3, by default the model's.
+
+    Returns {'frames': output index of every produced frame, 'stats': their [M,5] rows (min and max of the finite
+    values before clamping, elements below / above the output type's range, non-finite elements), 'totals',
+    'flow_frames', 'flow_parents', 'range', 'lo', 'span', 'buffer_uses' (chunks that went through each of the two
+    pinned buffers) and wall times 'time_total_s', 'time_setup_s' (in front of the first chunk: pinned and staging
+    buffers, the range pass), 'time_wait_s' (host waits on copy events), 'time_place_s' (host writes into the memory
+    maps), 'time_model_s', 'time_encode_s', 'time_d2h_s' (device time between events on the
+    streams, summed over chunks; 'time_d2h_chunk_s' per chunk)."""
+    if normalize not in NORMALIZE:
+        raise ValueError("normalize must be 'global' or 'none', got %r: one encode launch takes one (lo, span) pair, "
+                         "so the per-frame normalisation is not supported here" % (normalize,))
+    nd = int(nd if nd is not None else model.nd)
+    kind, K, sp = series_layout(stored.shape, nd)
+    if kind != "series":
+        raise ValueError("reconstruct takes a series [T,%s], got ready-made triplets %s" %
+                         (",".join("DHW"[3 - nd:]), tuple(stored.shape)))
+    if stored.dtype not in [np.dtype(t) for t in STORED_DTYPES]:
+        raise ValueError("stored must be uint8, uint16, float16 or float32, got %s" % stored.dtype)
+    if batch < 1:
+        raise ValueError("batch must be >= 1, got %d" % batch)
+    chunks = plan_chunks(K, exp, chunk)
+    factor = 2 ** exp
+    T_out, M = (K - 1) * factor + 1, (K - 1) * (factor - 1)
+    extra = tuple(stored.shape[1:stored.ndim - nd])  # () or (1,)
+    if tuple(writer.shape) != (T_out,) + extra + sp:
+        raise ValueError("the writer holds %s, the up-sampled series is %s" % (tuple(writer.shape), (T_out,) + extra + sp))
+    if flow_writer is not None:
+        if tuple(flow_writer.shape) != (M, 2 * nd) + sp:
+            raise ValueError("the flow writer holds %s, the flows are %s" % (tuple(flow_writer.shape), (M, 2 * nd) + sp))
+        if flow_writer.dtype not in (np.dtype(np.float16), np.dtype(np.float32)):
+            raise ValueError("flows are written as float16 or float32, got %s" % flow_writer.dtype)
+    frames_in = stored.reshape((K,) + sp)
+    out_dt = np.dtype(writer.dtype)
+    dev = next(model.flownet.parameters()).device
+    F = int(np.prod(sp))
+    m_max = min(chunk, K - 1) * (factor - 1)
+    n_keys = min(chunk, K - 1) + 1
+    flow_dt = None if flow_writer is None else np.dtype(flow_writer.dtype)
+    flow_bytes = 0 if flow_dt is None else m_max * 2 * nd * F * flow_dt.itemsize
+    t_start = time.perf_counter()
+    with torch.cuda.device(dev):
+        compute, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
+        slots = [_Slot(n_keys * F * stored.dtype.itemsize, m_max * F * out_dt.itemsize, flow_bytes, m_max)
+                 for _ in range(2)]
+        dev_keys = torch.empty((n_keys,) + sp, dtype=_torch_dtype(stored.dtype), device=dev)
+        key_bytes = dev_keys.view(torch.uint8).view(-1)
+
+        def stage_keys(slot, a, b):  # stored frames a..b-1 -> the slot's pinned bytes -> (n, their byte count)
+            n = b - a
+            host = slot.keys.numpy()[:n * F * stored.dtype.itemsize].view(stored.dtype).reshape((n,) + sp)
+            host[...] = frames_in[a:b]
+            return n, n * F * stored.dtype.itemsize
+
+        if normalize == "global" and norm_range is None:  # one pass over the file in front: the range of its finite values
+            rows = []
+            for a in range(0, K, n_keys):
+                n, nb = stage_keys(slots[0], a, min(a + n_keys, K))
+                key_bytes[:nb].copy_(slots[0].keys[:nb], non_blocking=True)
+                rows.append(ops.series_stats(dev_keys[:n].view(n, -1)).cpu().numpy())  # (waits for the copy too)
+            rows = np.concatenate(rows)
+            norm_range = (float(rows[:, 0].min()), float(rows[:, 1].max()))
+        lo, inv, span = normalisation(normalize, norm_range)
+
+        # everything a chunk needs from the host besides its keyframes goes up here, in front of the loop: inside it a
+        # pageable host-to-device copy would make the host wait for the compute stream (PyTorch synchronises behind one)
+        jobs = {}  # new keyframes of a chunk -> records that decode frames 0..n-1 of dev_keys, three per record
+        for ci, c in enumerate(chunks):
+            n = c["keys"][1] - c["keys"][0] + (1 if ci == 0 else 0)
+            if n not in jobs:
+                rec = np.zeros(-(-n // 3), ops.TRIPLET_JOB)
+                rec["off"] = np.minimum(np.arange(3 * len(rec)), n - 1).reshape(-1, 3) * F
+                rec["lo"], rec["inv"] = lo, inv
+                jobs[n] = ops.upload_triplet_jobs(rec, dev_keys, sp)
+        plans = {}  # keyframe pairs of a chunk -> (the bisection's index groups, indices of the frames it produces)
+        for c in chunks:
+            pairs = c["keys"][1] - c["keys"][0]
+            if pairs not in plans:
+                Tc = pairs * factor + 1
+                produced = None if pairs == 1 else torch.tensor([t for t in range(Tc) if t % factor], device=dev)
+                plans[pairs] = (bisection_groups(Tc, factor, batch, dev), produced)
+
+        stage = [torch.empty((m_max, 1) + sp, dtype=_torch_dtype(out_dt), device=dev) for _ in range(2)]
+        stage_stats = [torch.empty(m_max, 5, dtype=torch.float64, device=dev) for _ in range(2)]
+        stage_flow = [None, None] if flow_dt is None else [
+            torch.empty((m_max, 2 * nd) + sp, dtype=_torch_dtype(flow_dt), device=dev) for _ in range(2)]
+        uploaded, gathered, encoded = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
+        timers = []  # per chunk (model start, model end = encode start, encode end)
+        stats_rows = np.empty((M, 5), np.float64)
+        t_wait = t_place = 0.0
+        d2h = []
+        done = 0  # produced frames placed so far = the flow item index of the next one
+
+        def place(slot):  # host: the chunk the slot holds -> the memory maps
+            nonlocal t_wait, t_place, done
+            c = slot.pending
+            t0 = time.perf_counter()
+            slot.copied.synchronize()
+            t1 = time.perf_counter()
+            m = len(c["frames"])
+            got = slot.frames.numpy()[:m * F * out_dt.itemsize].view(out_dt).reshape((m,) + sp)
+            for j, t in enumerate(c["frames"]):
+                writer.write(t, got[j])
+            if flow_writer is not None:
+                fl = slot.flows.numpy()[:m * 2 * nd * F * flow_dt.itemsize].view(flow_dt).reshape((m, 2 * nd) + sp)
+                for j in range(m):
+                    flow_writer.write(done + j, fl[j])
+            stats_rows[done:done + m] = slot.stats.numpy()[:m]
+            k0, k1 = c["keys"]
+            for k in range(k0 if k0 == 0 else k0 + 1, k1 + 1):  # the keyframes: the stored values themselves
+                v = frames_in[k]
+                writer.write(k * factor, v if v.dtype == out_dt else encode_numpy(v.astype(np.float32), out_dt))
+            d2h.append(slot.d2h[0].elapsed_time(slot.d2h[1]) * 1e-3)
+            done += m
+            slot.pending = None
+            t_wait += t1 - t0
+            t_place += time.perf_counter() - t1
+
+        prev = None
+        t_loop = time.perf_counter()
+        for ci, c in enumerate(chunks):
+            slot = slots[ci % 2]  # free: its previous chunk was placed while the chunk in between computed
+            k0, k1 = c["keys"]
+            first = k0 if ci == 0 else k0 + 1  # the keyframe shared with the previous chunk is on the device already
+            n, nb = stage_keys(slot, first, k1 + 1)
+            with torch.cuda.stream(side):
+                side.wait_event(gathered)  # the previous chunk's decode has read dev_keys
+                key_bytes[:nb].copy_(slot.keys[:nb], non_blocking=True)
+                uploaded.record(side)
+            compute.wait_event(uploaded)
+            B = -(-n // 3)
+            keys = ops.triplet_gather(dev_keys, jobs[n], (B, 3) + sp).view((3 * B, 1) + sp)[:n]
+            gathered.record(compute)
+            padded = _pad32(keys, nd)
+            Tc = (k1 - k0) * factor + 1
+            seq = padded.new_zeros((Tc,) + tuple(padded.shape[1:]))
+            if ci == 0:
+                seq[::factor] = padded
+            else:
+                seq[0] = prev
+                seq[factor::factor] = padded
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record(compute)
+
+            def mid(a, b, pos, fstage=stage_flow[ci % 2]):
+                res = model.inference(a, b)
+                m = res[0]
+                m = m[2] if isinstance(m, list) else m
+                if fstage is not None:
+                    f = res[1][-1]  # flow_list[2]: [B, 2*nd, *padded]
+                    if nd == 3:  # a displacement, converted at the padded extents the model ran on (flow_eval.rife_flows)
+                        f = torch.cat([ops.rife3d_to_disp(f[:, :3].double()), ops.rife3d_to_disp(f[:, 3:6].double())],
+                                      1).float()
+                    f = f.contiguous()
+                    for j, p in enumerate(pos):
+                        s = p - p // factor - 1  # the frame's place among the chunk's produced frames
+                        ops.series_encode(f[j:j + 1], flow_dt, sp, out=fstage[s:s + 1], stats=False)
+                return m
+
+            groups, produced = plans[k1 - k0]
+            bisect_keyframes(seq, factor, batch, mid, groups)
+            ev[1].record(compute)
+            m = len(c["frames"])
+            # one keyframe pair: its new frames are one slice; more: gathered once so that ONE launch encodes them
+            new_frames = seq[1:factor] if produced is None else seq.index_select(0, produced)
+            _, st = ops.series_encode(new_frames, out_dt, sp, lo=float(lo), span=float(span), out=stage[ci % 2][:m])
+            stage_stats[ci % 2][:m].copy_(st)
+            ev[2].record(compute)
+            encoded.record(compute)
+            timers.append(ev)
+            with torch.cuda.stream(side):
+                side.wait_event(encoded)
+                slot.d2h[0].record(side)
+                nbo = m * F * out_dt.itemsize
+                slot.frames[:nbo].copy_(stage[ci % 2][:m].view(torch.uint8).view(-1), non_blocking=True)
+                if flow_dt is not None:
+                    nbf = m * 2 * nd * F * flow_dt.itemsize
+                    slot.flows[:nbf].copy_(stage_flow[ci % 2][:m].view(torch.uint8).view(-1), non_blocking=True)
+                slot.stats[:m].copy_(stage_stats[ci % 2][:m], non_blocking=True)
+                slot.d2h[1].record(side)
+                slot.copied.record(side)
+            slot.pending = c
+            slot.uses += 1
+            prev = seq[-1].clone()
+            del seq, padded, keys
+            other = slots[(ci + 1) % 2]
+            if other.pending is not None:  # the previous chunk: placed while this one computes
+                place(other)
+        for slot in (slots[len(chunks) % 2], slots[(len(chunks) + 1) % 2]):
+            if slot.pending is not None:
+                place(slot)
+        t_model = sum(e[0].elapsed_time(e[1]) for e in timers) * 1e-3
+        t_encode = sum(e[1].elapsed_time(e[2]) for e in timers) * 1e-3
+    frames = [t for c in chunks for t in c["frames"]]
+    parents = [p for c in chunks for p in c["parents"]]
+    totals = {"min": float(stats_rows[:, 0].min()), "max": float(stats_rows[:, 1].max()),
+              "n_low": int(stats_rows[:, 2].sum()), "n_high": int(stats_rows[:, 3].sum()),
+              "n_nonfinite": int(stats_rows[:, 4].sum())}
+    return {"frames": frames, "stats": stats_rows, "totals": totals,
+            "flow_frames": frames if flow_writer is not None else [],
+            "flow_parents": parents if flow_writer is not None else [],
+            "range": None if norm_range is None else [float(norm_range[0]), float(norm_range[1])],
+            "lo": float(lo), "span": float(span), "buffer_uses": [s.uses for s in slots],
+            "time_total_s": time.perf_counter() - t_start, "time_setup_s": t_loop - t_start, "time_wait_s": t_wait,
+            "time_place_s": t_place,
+            "time_model_s": t_model, "time_encode_s": t_encode, "time_d2h_s": float(sum(d2h)),
+            "time_d2h_chunk_s": d2h}
+
+
+def build_parser(nd):
+    sp = ",".join("DHW"[3 - nd:])
+    ap = argparse.ArgumentParser(
+        description="up-sample a stored series in time by 2**exp with the model and write it, in its stored type, to an "
+                    ".npy file.  Out of scope: factors that are not powers of two, --normalize frame (one encode launch "
+                    "takes one range) and UPFlow.")
+    ap.add_argument("--series", required=True, help=".npy / .npz series [T,%s] or [T,1,%s]: uint8, uint16, float16, "
+                                                    "float32 (float64 is narrowed); every frame is a keyframe" % (sp, sp))
+    ap.add_argument("--series_key", default=None, help="array name inside an .npz")
+    ap.add_argument("--exp", type=int, default=1, help="2**exp - 1 frames are rebuilt between two stored ones")
+    ap.add_argument("--out", required=True, help="the up-sampled series, .npy, [(T-1)*2**exp + 1, ...]")
+    ap.add_argument("--dtype", choices=("stored", "uint8", "uint16", "float16", "float32"), default="stored",
+                    help="type of --out (integers: clamped, rounded to nearest even; float16 saturates)")
+    ap.add_argument("--normalize", choices=NORMALIZE, default="global",
+                    help="what the model sees: the file's range mapped to [0,1] (the training default) or the values as stored")
+    ap.add_argument("--range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="the range for --normalize global instead of this file's own, e.g. the training file's")
+    ap.add_argument("--flows", default=None, metavar="FLOWS.npy",
+                    help="also write the flows of every rebuilt frame toward its two parents, [M,%d,%s] displacements: what "
+                         "flow_eval.rife_flows returns for the pair the model saw -- stored frames as they are, rebuilt "
+                         "parents as the padded frames the bisection keeps" % (2 * nd, sp))
+    ap.add_argument("--flow_dtype", choices=("float16", "float32"), default="float32")
+    ap.add_argument("--batch", type=int, default=1, help="midpoints per model call")
+    ap.add_argument("--chunk", type=int, default=1, help="keyframe pairs per chunk (device memory grows with it, not with T)")
+    ap.add_argument("--model", default="train_log", help="directory holding flownet.pkl")
+    ap.add_argument("--overwrite", action="store_true", help="replace --out / --flows if they exist")
+    ap.add_argument("--report", default=None, metavar="R.json", help="write the per-frame stats, flow parents and times here")
+    return ap
+
+
+def main(Model, nd, argv=None):
+    args = build_parser(nd).parse_args(argv)
+    stored = load_series(args.series, key=args.series_key, nd=nd)
+    kind, K, sp = series_layout(stored.shape, nd)
+    if kind != "series":
+        raise ValueError("--series takes a series [T,%s], got ready-made triplets %s" %
+                         (",".join("DHW"[3 - nd:]), tuple(stored.shape)))
+    if args.range is not None and args.normalize != "global":
+        raise ValueError("--range belongs to --normalize global")
+    factor = 2 ** args.exp
+    plan_chunks(K, args.exp, args.chunk)  # (refuses a bad exp / chunk before anything is created)
+    T_out, M = (K - 1) * factor + 1, (K - 1) * (factor - 1)
+    out_dt = stored.dtype if args.dtype == "stored" else np.dtype(args.dtype)
+    for path in (args.out, args.flows):  # (refused again by the writers; here before the model is built)
+        if path and os.path.exists(path) and not args.overwrite:
+            raise FileExistsError("%s exists: pass --overwrite to replace it" % path)
+    dev = torch.device("cuda")
+    model = Model(-1, device=dev)
+    try:
+        model.load_model("flownet.pkl", args.model)
+    except FileNotFoundError:
+        print("no flownet.pkl under %s: using random-init weights" % args.model)
+    model.eval()
+    extra = tuple(stored.shape[1:stored.ndim - nd])
+    writer = SeriesWriter(args.out, (T_out,) + extra + sp, out_dt, args.overwrite, source=args.series)
+    flow_writer = None
+    try:
+        if args.flows:
+            if os.path.realpath(args.flows) == os.path.realpath(args.out):
+                raise ValueError("--flows and --out name the same file")
+            flow_writer = SeriesWriter(args.flows, (M, 2 * nd) + sp, args.flow_dtype, args.overwrite, source=args.series)
+        res = reconstruct_series(model, stored, args.exp, writer, args.batch, args.chunk, args.normalize, args.range,
+                                 flow_writer)
+    except BaseException:  # a partly written file looks like a result: remove what this run created
+        for w in (writer, flow_writer):
+            if w is not None:
+                w.close()
+                os.remove(w.path)
+        raise
+    writer.close()
+    if flow_writer is not None:
+        flow_writer.close()
+    t = res["totals"]
+    print("wrote %d frames (%d rebuilt) %s %s to %s: %d elements clipped (%d low, %d high), %d non-finite, %.4f s per "
+          "rebuilt frame" % (T_out, M, out_dt, tuple(sp), args.out, t["n_low"] + t["n_high"], t["n_low"], t["n_high"],
+                             t["n_nonfinite"], res["time_total_s"] / max(M, 1)))
+    doc = dict(res, series=os.path.basename(args.series), out=args.out, flows=args.flows, dtype=str(out_dt),
+               shape=[T_out] + list(extra + sp), exp=args.exp, batch=args.batch, chunk=args.chunk,
+               normalize=args.normalize, stats=[dict(zip(STAT_NAMES, (float(v) for v in r))) for r in res["stats"]])
+    if args.report:
+        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
+        with open(args.report, "w") as f:
+            json.dump(json_safe(doc), f, indent=1, allow_nan=False)
+    return doc
+
+
+def json_safe(x):
+    """`x` with every float that JSON cannot hold (the +inf / -inf minimum and maximum of a frame without a finite value,
+    NaN) replaced by None."""
+    if isinstance(x, dict):
+        return {k: json_safe(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [json_safe(v) for v in x]
+    if isinstance(x, float) and not np.isfinite(x):
+        return None
+    return x
