@@ -51,8 +51,9 @@ enum {
  *   380  fs_flow_consistency2d / fs_flow_consistency3d and their _ws_bytes queries (label-free flow quality:
  *        forward-backward residual, occlusion / outgoing / consistent classes, photometric error of the warp).
  *   390  fs_series_encode / fs_series_encode_ws_bytes (padded fp32 planes back to a stored type: the inverse of the
- *        gather's decode, for writing rebuilt series and flows). */
-#define FS_ABI_VERSION 390
+ *        gather's decode, for writing rebuilt series and flows).
+ *   400  fs_advect2d / fs_advect3d (pathlines: particles advected through consecutive displacement fields). */
+#define FS_ABI_VERSION 400
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -755,6 +756,51 @@ int fs_flow_consistency3d(const float* flow_f, const float* flow_b, int N, int C
                           long long f_bstride, long long b_bstride, const float* img0, const float* img1,
                           const unsigned char* valid, double alpha1, double alpha2, unsigned char* class_map,
                           float* res_map, double* ws, double* out, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Pathlines -- P particles moved through K consecutive displacement fields, one launch.
+ *   flows: K fields of C fp32 planes of D*H*W elements (2-D: D = 1, C = 2; 3-D: C = 3), planes of one field contiguous,
+ *     field k at + k * flow_sstride elements (flow_sstride >= C*D*H*W when K > 1); channel 0 along W, 1 along H, 2 along
+ *     D, in elements.  Field k is the displacement over time step k on that step's grid.
+ *   pos_in: fp32 [C][P], component c at + c * pos_cstride (>= P); component 0 is x (along W).
+ *   traj: fp32 [K][C][P], step k at + k * traj_sstride (>= P when K > 1), component c at + c * traj_cstride (>= P): the
+ *     position after step k goes to slot k.  traj_sstride = 0 keeps the last position only (a particle's stores go out
+ *     in step order to the one slot).  Slot K-1 may be pos_in's memory (same pointer and component stride): a
+ *     particle's pos_in is read once, before any store, and no thread touches another particle's elements.
+ *   status: uint8 [P], in / out, FS_ADV_ALIVE / FS_ADV_OUT / FS_ADV_NONFINITE.  steps: int32 [P], in / out, or NULL: the
+ *     number of steps after which the particle was still ALIVE is added.
+ *   method: FS_ADV_EULER, FS_ADV_RK2 (midpoint) or FS_ADV_RK4; substeps S >= 1; hs = scale / S, 0.5 * hs and hs / 6.0
+ *     are formed on the host in fp64 (scale = -1 with the opposite flows traces backward in time).
+ *   Per particle, in fp64 without fused multiply-adds (a restatement with the same operations in the same order
+ *   reproduces every output bit, status and count):
+ *     sample(k, q): any q_c not finite -> every component NaN (no index is formed).  Else q_c = min(max(q_c, 0), S_c - 1),
+ *       i0 = floor(q_c), f_c = q_c - i0, g_c = 1 - f_c, i1 = min(i0 + 1, S_c - 1); the corner with bits (bz, by, bx) weighs
+ *       (tz * ty) * tx (2-D: ty * tx), t = f where the bit is set, else g; the sum over the corners in ascending
+ *       4 bz + 2 by + bx, from 0.0, of weight * flows_k,c[corner], every product formed (a non-finite corner of weight 0
+ *       gives NaN).
+ *     classify(p): any p_c not finite: NONFINITE.  Else p_c < 0 or p_c > S_c - 1 for some c: OUT (the border is inside).
+ *       Else ALIVE.
+ *     Step k: the fp32 position (pos_in at k = 0, the previous step's result later) is widened; an ALIVE particle is
+ *       classified (a seed outside the box or a non-finite seed ends here without moving).  For s in 0..S-1 while ALIVE,
+ *       with k1 = sample(k, p): Euler p' = p + hs k1; RK2 k2 = sample(p + (0.5 hs) k1), p' = p + hs k2; RK4 the classical
+ *       stages k2 = sample(p + (0.5 hs) k1), k3 = sample(p + (0.5 hs) k2), k4 = sample(p + hs k3),
+ *       p' = p + (hs / 6) (((k1 + 2 k2) + 2 k3) + k4).  Stage points are clamped by sample and never classified.
+ *       classify(p'): NONFINITE keeps p; OUT takes p' (the exit point); ALIVE takes p'.  After the substeps an ALIVE
+ *       particle's `steps` grows by one; the position is rounded to fp32 once and stored in slot k; the next step starts
+ *       from the rounded value, so K steps in one launch equal K launches of one step bit for bit.  A particle that is
+ *       not ALIVE (on entry too) copies its position to every remaining slot.
+ *   FS_ERR_NULLPTR: flows, pos_in, traj or status NULL.  FS_ERR_SHAPE: K < 1, P < 1, C other than 2 (2-D) / 3 (3-D), an
+ *   extent < 1, a stride below its minimum.  FS_ERR_ARG: substeps < 1, an unknown method, scale not finite.  All of them
+ *   are returned before anything is launched.
+ */
+enum { FS_ADV_ALIVE = 0, FS_ADV_OUT = 1, FS_ADV_NONFINITE = 2 };
+enum { FS_ADV_EULER = 0, FS_ADV_RK2 = 1, FS_ADV_RK4 = 2 };
+int fs_advect2d(const float* flows, int K, int C, int H, int W, long long flow_sstride, const float* pos_in,
+                long long pos_cstride, long long P, float* traj, long long traj_sstride, long long traj_cstride,
+                unsigned char* status, int* steps, int method, int substeps, double scale, fs_stream_t stream);
+int fs_advect3d(const float* flows, int K, int C, int D, int H, int W, long long flow_sstride, const float* pos_in,
+                long long pos_cstride, long long P, float* traj, long long traj_sstride, long long traj_cstride,
+                unsigned char* status, int* steps, int method, int substeps, double scale, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

@@ -2682,6 +2682,140 @@ def _consistency_stats(out, images):
 
 
 # --------------------------------------------------------------------------------------------
+# Pathlines: particles advected through consecutive displacement fields (fs_advect{2,3}d)
+# --------------------------------------------------------------------------------------------
+ADV_ALIVE, ADV_OUT, ADV_NONFINITE = 0, 1, 2  # FS_ADV_*: status codes
+_ADV_METHODS = {"euler": (0, 1), "rk2": (1, 2), "rk4": (2, 4)}  # name -> (FS_ADV_*, samples per substep)
+
+
+def advect_cost(shape, P, K, method="euler", substeps=1, record=False):
+    """(HBM bytes, flops) the algorithm needs for one advect call of P particles through K fields of spatial `shape`:
+    every field element the gathers can reach read once (at most the whole fields, at most what the
+    K * substeps * stages samples of 2^C corners x C planes ask for), pos_in read and the positions written once (per
+    step with record), status and steps read and written.  Flops per sample: the 2^C corner weights (C - 1 products
+    each), 2 per corner and plane, ~4 C for clamp / floor / fractions, 2 C for the stage point; ~4 C per substep for
+    the update and its classification (RK4: 5 C more for the stage sum)."""
+    if method not in _ADV_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(_ADV_METHODS), method))
+    C = len(shape)
+    plane = 1
+    for s in shape:
+        plane *= int(s)
+    stages = _ADV_METHODS[method][1]
+    samples = int(P) * int(K) * int(substeps) * stages
+    field = 4 * min(int(K) * C * plane, samples * (1 << C) * C)
+    nbytes = field + 4 * C * int(P) * (1 + (int(K) if record else 1)) + 2 * int(P) + 8 * int(P)
+    per_sample = (1 << C) * (C - 1) + 2 * (1 << C) * C + 4 * C + 2 * C
+    flops = samples * per_sample + int(P) * int(K) * int(substeps) * (4 * C + (5 * C if method == "rk4" else 0))
+    return nbytes, flops
+
+
+def grid_seeds(shape, stride=1, offset=0, device="cuda"):
+    """[C, P] fp32 positions of every `stride`-th element of a grid of spatial `shape` ((H,W) or (D,H,W)), starting at
+    `offset` along every axis, x fastest: component 0 is x (along W).  With stride 1 and offset 0,
+    seeds.view(C, *shape) is the identity field and a [C, P] result views as a [C, *shape] displacement."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (2, 3) or min(shape) < 1:
+        raise ValueError("shape must be (H,W) or (D,H,W) with every extent >= 1, got %r" % (shape,))
+    stride, offset = int(stride), int(offset)
+    if stride < 1 or offset < 0:
+        raise ValueError("stride must be >= 1 and offset >= 0, got %d and %d" % (stride, offset))
+    axes = [torch.arange(offset, s, stride, dtype=torch.float32, device=device) for s in shape]  # slowest first
+    mesh = torch.meshgrid(*axes, indexing="ij")
+    return torch.stack([m.reshape(-1) for m in mesh[::-1]], 0).contiguous()
+
+
+def _advect_flows(flows):
+    """[K,C,*sp] fp32 on a GPU whose [C,*sp] block per step is contiguous: the step stride may be anything from
+    C * prod(sp) up (a stack's every other field, flows[::2], passes as it is); anything else is copied once."""
+    if not isinstance(flows, torch.Tensor) or flows.dim() not in (4, 5):
+        raise ValueError("flows must be [K,2,H,W] or [K,3,D,H,W], got %s" %
+                         (tuple(flows.shape) if isinstance(flows, torch.Tensor) else type(flows).__name__,))
+    nd = flows.dim() - 2
+    if flows.shape[0] < 1:
+        raise ValueError("flows must hold at least one field, got shape %s" % (tuple(flows.shape),))
+    return _flow_operand("flows", flows.detach(), nd), nd
+
+
+def advect(pos, flows, status=None, steps=None, method="euler", substeps=1, scale=1.0, record=False):
+    """Move P particles through K consecutive displacement fields in one launch (fs_advect{2,3}d).
+
+    pos: [C,P] fp32 on a GPU, component 0 = x (along W), 1 = y, 2 = z, in elements; rows may be strided (a [C,P] slice
+    of a trajectory passes as it is), elements of a row are contiguous.  flows: [K,2,H,W] or [K,3,D,H,W] displacements
+    in elements (channel 0 along W), field k being the motion over step k on that step's grid; the step stride may be
+    anything.  status: optional uint8 [P] of an earlier call (ADV_ALIVE 0, ADV_OUT 1, ADV_NONFINITE 2); None = all
+    ALIVE.  steps: optional int32 [P] counts to continue, None to start from 0, False to count nothing (None comes back).
+    Neither is modified: the returned tensors are new.  method: "euler", "rk2" (midpoint) or "rk4", each step in
+    `substeps` equal parts through the step's own (steady) field; the update is p + (scale / substeps) * velocity.
+
+    All arithmetic is fp64 (include/flowsci_hip.h states the order of operations; tests/advect_ref.py restates it and
+    agrees bit for bit); positions are stored as fp32 once per step.  A particle ends when it leaves the box (OUT: it
+    keeps its exit point; the border is inside) or meets a non-finite value (NONFINITE: it keeps its last finite
+    position); a seed outside the box or not finite ends without moving.
+
+    Returns (pos_out [C,P], status, steps), or with record=True (traj [K+1,C,P] with traj[0] = pos, status, steps).
+    Never synchronises.  A measurement on detached values: nothing is differentiated."""
+    if method not in _ADV_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(_ADV_METHODS), method))
+    substeps = int(substeps)
+    if substeps < 1:
+        raise ValueError("substeps must be >= 1, got %d" % substeps)
+    scale = float(scale)
+    if not (-float("inf") < scale < float("inf")):
+        raise ValueError("scale must be finite, got %r" % (scale,))
+    flows, nd = _advect_flows(flows)
+    dev = flows.device
+    if not isinstance(pos, torch.Tensor):
+        raise ValueError("pos must be a tensor")
+    if not pos.is_cuda:
+        raise ValueError("pos must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (pos.device,))
+    if pos.device != dev:
+        raise ValueError("pos must be on the flows' device %s, got %s" % (dev, pos.device))
+    if pos.dim() != 2 or pos.shape[0] != nd:
+        raise ValueError("pos must be [%d,P] for %d-D flows, got shape %s" % (nd, nd, tuple(pos.shape)))
+    pos = pos.detach()
+    if pos.dtype != torch.float32:
+        pos = pos.to(torch.float32)
+    K, P = int(flows.shape[0]), int(pos.shape[1])
+    if P > 0 and (pos.stride(1) != 1 or pos.stride(0) < P):
+        pos = pos.contiguous()
+
+    def state(name, t, dtype):
+        if t is None:
+            return torch.zeros(P, dtype=dtype, device=dev)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (P,):
+            raise ValueError("%s must be a %s tensor of shape (%d,), got %s" % (
+                name, dtype, P, (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if t.device != dev:
+            raise ValueError("%s must be on the flows' device %s, got %s" % (name, dev, t.device))
+        return t.clone(memory_format=torch.contiguous_format)
+
+    status = state("status", status, torch.uint8)
+    steps = None if steps is False else state("steps", steps, torch.int32)
+    if record:
+        traj = torch.empty(K + 1, nd, P, dtype=torch.float32, device=dev)
+        traj[0].copy_(pos)
+        out, tss = traj[1:], nd * P
+    else:
+        traj = out = torch.empty(nd, P, dtype=torch.float32, device=dev)
+        tss = 0  # every step overwrites the one slot
+    if P == 0:
+        return traj, status, steps
+    sp = tuple(int(s) for s in flows.shape[2:])
+    plane = 1
+    for v in sp:
+        plane *= v
+    fss = flows.stride(0) if K > 1 else nd * plane  # (a single field's step stride is never used)
+    nbytes, flops = advect_cost(sp, P, K, method, substeps, record)
+    args = (flows.data_ptr(), K, nd) + sp + (fss, pos.data_ptr(), pos.stride(0), P,
+                                             out.data_ptr(), tss, P, status.data_ptr(), _ptr(steps),
+                                             _ADV_METHODS[method][0], substeps, scale, _stream(flows))
+    with torch.cuda.device(dev):
+        _call("fs_advect%dd" % nd, *args, algo_bytes=nbytes, algo_flops=flops)
+    return traj, status, steps
+
+
+# --------------------------------------------------------------------------------------------
 # Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
 # --------------------------------------------------------------------------------------------
 import numpy as _np
