@@ -52,8 +52,9 @@ enum {
  *        forward-backward residual, occlusion / outgoing / consistent classes, photometric error of the warp).
  *   390  fs_series_encode / fs_series_encode_ws_bytes (padded fp32 planes back to a stored type: the inverse of the
  *        gather's decode, for writing rebuilt series and flows).
- *   400  fs_advect2d / fs_advect3d (pathlines: particles advected through consecutive displacement fields). */
-#define FS_ABI_VERSION 400
+ *   400  fs_advect2d / fs_advect3d (pathlines: particles advected through consecutive displacement fields).
+ *   410  fs_ftle2d / fs_ftle3d and their _ws_bytes queries (finite-time Lyapunov exponents of a lattice flow map). */
+#define FS_ABI_VERSION 410
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -801,6 +802,57 @@ int fs_advect2d(const float* flows, int K, int C, int H, int W, long long flow_s
 int fs_advect3d(const float* flows, int K, int C, int D, int H, int W, long long flow_sstride, const float* pos_in,
                 long long pos_cstride, long long P, float* traj, long long traj_sstride, long long traj_cstride,
                 unsigned char* status, int* steps, int method, int substeps, double scale, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * FTLE -- the finite-time Lyapunov exponent of a flow map sampled on a lattice, one launch (plus the summary's).
+ *   map: fp32 [C][Gd*Gh*Gw], component c at + c * map_cstride (>= Gd*Gh*Gw) elements, node (z, y, x) at
+ *     (z * Gh + y) * Gw + x (x fastest): the end positions fs_advect* returns for lattice seeds.  2-D: Gd = 1, C = 2;
+ *     3-D: C = 3.  Component 0 and axis 0 run along x.
+ *   status: uint8 [Gd*Gh*Gw], the FS_ADV_* of fs_advect*.  valid: uint8 [Gd*Gh*Gw] (nonzero = set) or NULL = every node.
+ *   inv_h, inv_2h: HOST arrays of C doubles, 1 / h_c and 1 / (2 h_c) with h_c the seed spacing along axis c in elements;
+ *     inv_T = 1 / |integration time|.  The host forms them in fp64; the device divides nothing by them.
+ *   Per node, in fp64 without fused multiply-adds up to and including G (a restatement with the same operations in the
+ *   same order reproduces every class and every bit of cg):
+ *     usable(j): status[j] == FS_ADV_ALIVE, or FS_ADV_OUT when accept_out != 0 (the exit point stands for the end
+ *       position).
+ *     The difference along axis c at index i is the first that applies of: central, i-1 and i+1 exist and are usable
+ *       (the node's own state does not matter): (phi(i+1) - phi(i-1)) * inv_2h[c]; forward, i and i+1 usable:
+ *       (phi(i+1) - phi(i)) * inv_h[c]; backward, i and i-1 usable: (phi(i) - phi(i-1)) * inv_h[c].  None along some axis:
+ *       FS_FTLE_ENDED.  Map values are widened to fp64 before the subtraction; nothing is read from a node that is not
+ *       usable (its map values may be anything).
+ *     J[r][c] = the difference of component r along axis c.  Any J[r][c] not finite (a used map value was not):
+ *       FS_FTLE_NONFINITE.
+ *     G[a][b] = (J[0][a] J[0][b] + J[1][a] J[1][b]) + J[2][a] J[2][b] (2-D: the first two terms), the Cauchy-Green tensor.
+ *     lambda = its largest eigenvalue: in 2-D 0.5 (G00 + G11) + sqrt((0.5 (G00 - G11))^2 + G01^2), in 3-D by cyclic
+ *       Jacobi rotations on G scaled by a power of two, until the off-diagonal entries sum to less than 2^-45 of the
+ *       scaled trace's upper bound (relative error of lambda below 2e-13; a diagonal G gives its largest entry exactly).
+ *     lambda == 0: FS_FTLE_COLLAPSED (the lattice cell mapped to a point).  Else e = (0.5 * log(lambda)) * inv_T, rounded
+ *       to fp32 once; e not finite: FS_FTLE_NONFINITE; else FS_FTLE_OK.
+ *   ftle: fp32 [Gd*Gh*Gw]: e where the class is FS_FTLE_OK, NaN elsewhere.  cls: uint8 [Gd*Gh*Gw]: FS_FTLE_NOT_VALID where
+ *     valid is not set, else the class.
+ *   cg: fp32 [C(C+1)/2][Gd*Gh*Gw] or NULL: G's entries in the plane order xx, xy, yy, xz, yz, zz, each rounded once; NaN at
+ *     nodes that are neither OK nor COLLAPSED.
+ *   out: fp64 [FS_FTLE_K] or NULL: 0-4 the number of nodes of class 0-4; 5 the sum, 6 the sum of squares, 7 the minimum
+ *     (+inf when none) and 8 the maximum (-inf when none) of the STORED fp32 ftle over the OK nodes.  Per-workgroup fp64
+ *     partials in `ws` (fs_ftle{2,3}d_ws_bytes bytes, 8-byte aligned; needed only with out), combined by a second launch
+ *     in a fixed order: bitwise reproducible, no atomics.
+ *   FS_ERR_NULLPTR: map, status, inv_h, inv_2h, ftle or cls NULL, or out without ws.  FS_ERR_SHAPE: C other than 2 (2-D) /
+ *   3 (3-D), a lattice extent below 2 along an axis C covers, more than 2^31 - 1 nodes, map_cstride below the node count.
+ *   FS_ERR_ARG: an inv_h[c], inv_2h[c] or inv_T that is not finite or not positive.  All of them are returned before
+ *   anything is launched.  The _ws_bytes queries launch nothing and return the byte count or -(FS_ERR_*).
+ */
+#define FS_FTLE_K 9
+#define FS_FTLE_MIN 7
+#define FS_FTLE_MAX 8
+enum { FS_FTLE_NOT_VALID = 0, FS_FTLE_OK = 1, FS_FTLE_ENDED = 2, FS_FTLE_NONFINITE = 3, FS_FTLE_COLLAPSED = 4 };
+long long fs_ftle2d_ws_bytes(int C, int Gh, int Gw);
+long long fs_ftle3d_ws_bytes(int C, int Gd, int Gh, int Gw);
+int fs_ftle2d(const float* map, long long map_cstride, const unsigned char* status, const unsigned char* valid, int C,
+              int Gh, int Gw, const double* inv_h, const double* inv_2h, double inv_T, int accept_out, float* ftle,
+              unsigned char* cls, float* cg, double* ws, double* out, fs_stream_t stream);
+int fs_ftle3d(const float* map, long long map_cstride, const unsigned char* status, const unsigned char* valid, int C,
+              int Gd, int Gh, int Gw, const double* inv_h, const double* inv_2h, double inv_T, int accept_out,
+              float* ftle, unsigned char* cls, float* cg, double* ws, double* out, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

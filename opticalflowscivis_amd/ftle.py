@@ -1,0 +1,246 @@
+"""FTLE fields: where the transport barriers of a series' estimated flows are.  A lattice of particles is advected
+through `window` consecutive step flows (ops.advect), the resulting flow map is differentiated and reduced to the
+finite-time Lyapunov exponent ln(sqrt(lambda_max(J^T J))) / |T| on the device (ops.ftle); a new window opens every
+`every` steps.  Forward in time the ridges of the field are the repelling structures, backward (--direction bwd) the
+attracting ones.  Shared by the flow2d / flow3d / upflow `ftle` entry points:
+
+    python -m opticalflowscivis_amd.flow3d.ftle --seq frames.npy --window 4 --every 2 --refine 2 --direction bwd \
+        --method rk4 --out ftle.npy --classes cls.npy --json r.json
+    python -m opticalflowscivis_amd.flow2d.ftle --flows flows.npy --window 3 --out ftle.npy
+    python -m opticalflowscivis_amd.upflow.ftle --dataset rectangle2d --window 2 --json r.json
+
+The step flows are those of `trace` (trace.step_chain over the flows flow_eval extracts, or --flows).  Windows overlap
+when every < window; each step flow is still estimated once: when step j's flow arrives, every open window's particle set
+advances by one ops.advect launch of one step, which the kernel guarantees to equal its share of a `window`-step launch
+bit for bit.  Device memory is ceil(window / every) particle sets, one `--chunk` of flows and the result stack.
+
+The lattice refines the grid `--refine` times ((S - 1) * refine + 1 nodes per axis, spacing 1 / refine elements).  The
+integration time T is the frames a window spans times --dt.  A node whose neighbourhood left the box has no FTLE (class 2,
+NaN); --accept-out lets a particle that left stand in with its exit point.  Classes: 0 not valid, 1 ok, 2 ended,
+3 nonfinite, 4 collapsed.
+
+Out of scope: eigenvectors and ridge extraction; several series in one launch; autograd through the op."""
+import argparse
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import flow_eval, ops, trace
+
+
+def window_starts(n_steps, window, every):
+    """The steps of the chain at which a window of `window` steps opens: every `every`-th one that still closes."""
+    window, every = int(window), int(every)
+    if window < 1 or every < 1:
+        raise ValueError("window and every must be >= 1, got %d and %d" % (window, every))
+    return list(range(0, int(n_steps) - window + 1, every))
+
+
+def ftle_series(step_flows, n_steps, sp, window, every=1, refine=1, method="euler", substeps=1, chunk=4, scale=1.0,
+                accept_out=False, frames=None, dt=1.0, with_cg=False):
+    """FTLE fields of every window of `window` steps, opened every `every` steps, of the n_steps step flows that
+    step_flows(j0, j1) -> [j1 - j0, C, *sp] hands out `chunk` at a time (each exactly once).  frames: the n_steps + 1
+    frames the chain visits (default 0..n_steps); a window's T is the frames it spans times dt.
+
+    Returns a dict: ftle (fp32 [n_windows, *lattice]), cls (uint8, the same shape), cg ([n_windows, C(C+1)/2, *lattice],
+    with_cg only), lattice, spacing, windows (one dict per window: step, t_from, t_to, frames_spanned, T, counts, mean,
+    std, min, max, time_inference_s, time_advect_s, time_ftle_s) and the totals time_flows_s, time_advect_s,
+    time_ftle_s.  A window's time_inference_s is its share of the chunks that held its steps (overlapping windows share
+    flows, so the windows' shares add up to more than time_flows_s)."""
+    chunk = max(1, int(chunk))
+    starts = window_starts(n_steps, window, every)
+    frames = list(range(n_steps + 1)) if frames is None else list(frames)
+    if len(frames) != n_steps + 1:
+        raise ValueError("frames must name the %d frames the chain visits, got %d" % (n_steps + 1, len(frames)))
+    dt = float(dt)
+    if not (0 < dt < float("inf")):
+        raise ValueError("dt must be finite and positive, got %r" % (dt,))
+    dev = torch.device("cuda")
+    seeds, lattice, spacing = ops.lattice_seeds(sp, refine, dev)
+    nd, nw = len(lattice), len(starts)
+    res = {"ftle": torch.empty((nw,) + lattice, dtype=torch.float32, device=dev),
+           "cls": torch.empty((nw,) + lattice, dtype=torch.uint8, device=dev), "lattice": lattice, "spacing": spacing}
+    if with_cg:
+        res["cg"] = torch.empty((nw, nd * (nd + 1) // 2) + lattice, dtype=torch.float32, device=dev)
+    rows = [{"step": s, "t_from": frames[s], "t_to": frames[s + window],
+             "frames_spanned": abs(frames[s + window] - frames[s]), "time_inference_s": 0.0, "time_advect_s": 0.0,
+             "time_ftle_s": 0.0} for s in starts]
+    summaries = [None] * nw
+    is_open = {}  # window index -> (pos, status)
+    t_flows = t_adv = t_ftle = 0.0
+    last = starts[-1] + window if starts else 0  # no flow past the last closing window is asked for
+    for j0 in range(0, last, chunk):
+        j1 = min(last, j0 + chunk)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f = step_flows(j0, j1)
+        torch.cuda.synchronize()
+        per_step = (time.perf_counter() - t0) / (j1 - j0)
+        t_flows += per_step * (j1 - j0)
+        for j in range(j0, j1):
+            if j % every == 0 and j + window <= n_steps:
+                is_open[j // every] = (seeds, None)
+            for w in sorted(is_open):
+                pos, status = is_open[w]
+                t1 = time.perf_counter()
+                pos, status, _ = ops.advect(pos, f[j - j0:j - j0 + 1], status, False, method, substeps, scale)
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                rows[w]["time_inference_s"] += per_step
+                rows[w]["time_advect_s"] += t2 - t1
+                t_adv += t2 - t1
+                is_open[w] = (pos, status)
+                if j + 1 == starts[w] + window:
+                    T = rows[w]["frames_spanned"] * dt
+                    rows[w]["T"] = T
+                    r = ops.ftle(pos, status, lattice, spacing, T, accept_out=accept_out, with_cg=with_cg)
+                    res["ftle"][w].copy_(r["ftle"])
+                    res["cls"][w].copy_(r["cls"])
+                    if with_cg:
+                        res["cg"][w].copy_(r["cg"])
+                    summaries[w] = r["summary"]
+                    torch.cuda.synchronize()
+                    rows[w]["time_ftle_s"] = time.perf_counter() - t2
+                    t_ftle += rows[w]["time_ftle_s"]
+                    del is_open[w]
+    for w, s in enumerate(summaries):
+        rows[w].update(ops.ftle_stats(s))
+    res.update(windows=rows, time_flows_s=t_flows, time_advect_s=t_adv, time_ftle_s=t_ftle)
+    return res
+
+
+def _args(nd, desc, model):
+    sp = ",".join("DHW"[3 - nd:])
+    ap = argparse.ArgumentParser(description=desc)
+    ap.add_argument("--dataset", choices=flow_eval.DATASETS[nd], help="synthetic sequence with known motion")
+    ap.add_argument("--seq", help=".npy sequence [T,%s] in [0,1]" % sp)
+    ap.add_argument("--flows", metavar="PATH", help="skip the model: a [K,%d,%s] .npy of consecutive step flows, or a "
+                    "directory of flow_%%03d_to_%%03d.npy files chained from --start" % (nd, sp))
+    ap.add_argument("--start", type=int, default=0, help="first frame of a --flows chain")
+    ap.add_argument("--frames", type=int, default=9, help="frames of a synthetic sequence")
+    ap.add_argument("--size", type=int, nargs="+", default=None, help="synthetic extent (S, or H W in 2-D)")
+    ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--gap", type=int, default=1 if model == "upflow" else 2,
+                    help="the model runs on pairs (t, t+gap)" + ("" if model == "upflow" else ": a step spans gap / 2 frames"))
+    ap.add_argument("--model", default="train_log", help="directory holding the weights")
+    ap.add_argument("--batch", type=int, default=1, help="pairs per model call")
+    ap.add_argument("--window", type=int, required=True, help="steps of the chain a flow map integrates over")
+    ap.add_argument("--every", type=int, default=1, help="a window opens at every EVERY-th step of the chain")
+    ap.add_argument("--refine", type=int, default=1, help="lattice nodes per grid element along every axis")
+    ap.add_argument("--direction", choices=("fwd", "bwd"), default="fwd",
+                    help="fwd: repelling structures; bwd: attracting ones (the model's own backward flows)")
+    ap.add_argument("--method", choices=sorted(ops._ADV_METHODS), default="euler")
+    ap.add_argument("--substeps", type=int, default=1)
+    ap.add_argument("--chunk", type=int, default=4, help="step flows estimated at a time")
+    ap.add_argument("--accept-out", action="store_true", help="a particle that left the box counts with its exit point")
+    ap.add_argument("--dt", type=float, default=1.0, help="the time one frame spans: T = frames spanned * dt")
+    ap.add_argument("--out", default=None, metavar="FTLE.npy", help="write the fields [n_windows, *lattice] (fp32) here")
+    ap.add_argument("--classes", default=None, metavar="CLS.npy", help="write the class maps (uint8, the same shape) here")
+    ap.add_argument("--json", default=None, help="write the report as JSON here")
+    return ap
+
+
+def check_args(args):
+    """What the parser cannot express."""
+    if sum(x is not None for x in (args.dataset, args.seq, args.flows)) == 0:
+        raise SystemExit("one of --dataset, --seq and --flows is needed")
+    if args.dataset and args.seq:
+        raise SystemExit("--dataset and --seq exclude each other")
+    for name in ("window", "every", "refine", "substeps", "chunk"):
+        if getattr(args, name) < 1:
+            raise SystemExit("--%s must be >= 1" % name)
+    if args.start < 0:
+        raise SystemExit("--start must be >= 0")
+    if not (0 < args.dt < float("inf")):
+        raise SystemExit("--dt must be finite and positive")
+    return args
+
+
+def run(args, nd, model, make_model):
+    """The FTLE fields of one parsed command line.  make_model() -> flows(frames, pairs) -> [2P, C, *sp]."""
+    dev = torch.device("cuda")
+    frames = None
+    name = args.dataset or os.path.basename(args.seq or args.flows.rstrip("/"))
+    if args.dataset:
+        frames, _ = flow_eval.motion(args.dataset, args.frames, args.size, args.seed, dev)
+    elif args.seq:
+        frames = torch.from_numpy(np.load(args.seq).astype(np.float32)).to(dev)
+        if frames.dim() != nd + 1:
+            raise SystemExit("--seq must be [T,%s], got %s" % (",".join("DHW"[3 - nd:]), tuple(frames.shape)))
+    if args.flows:
+        visited, load, sp = trace._given_flows(args, nd)
+        source = lambda j0, j1: torch.from_numpy(load(j0, j1)).to(dev)
+    else:
+        sp = tuple(int(s) for s in frames.shape[1:])
+        chain = trace.step_chain(frames.shape[0], args.gap, args.direction, model)
+        visited = ([chain[0][0]] + [c[1] for c in chain]) if chain else []
+        if model == "rife":
+            pairs = flow_eval.rife_pairs(frames.shape[0], args.gap)
+        else:
+            pairs = [(t, t + args.gap) for t in range(0, frames.shape[0] - args.gap)]
+        flows_of = make_model() if chain else None
+
+        def source(j0, j1):
+            # the chain's flows of one direction share their parity in the model's (first, second) flow stack
+            part = chain[j0:j1]
+            stack = flows_of(frames, [pairs[c[2] // 2] for c in part])
+            return stack[part[0][2] % 2::2]
+    K = max(0, len(visited) - 1)
+    res = ftle_series(source, K, sp, args.window, args.every, args.refine, args.method, args.substeps, args.chunk,
+                      accept_out=args.accept_out, frames=visited or [0], dt=args.dt)
+    doc = {"sequence": name, "shape": list(sp), "lattice": list(res["lattice"]), "spacing": res["spacing"],
+           "model": None if args.flows else args.model, "direction": args.direction, "method": args.method,
+           "substeps": args.substeps, "chunk": args.chunk, "gap": args.gap, "window": args.window, "every": args.every,
+           "refine": args.refine, "accept_out": bool(args.accept_out), "dt": args.dt, "frames": visited,
+           "windows": res["windows"], "time_inference_s": res["time_flows_s"], "time_advect_s": res["time_advect_s"],
+           "time_ftle_s": res["time_ftle_s"]}
+    if not res["windows"]:
+        print("%s: the chain has %d steps, too few for a window of %d" % (name, K, args.window))
+    for w in res["windows"]:
+        print("%s %s frames %d..%d (T %g): ok %d  ended %d  nonfinite %d  collapsed %d  | ftle mean %.4f std %.4f "
+              "min %.4f max %.4f" % (name, args.direction, w["t_from"], w["t_to"], w["T"], w["counts"]["ok"],
+                                     w["counts"]["ended"], w["counts"]["nonfinite"], w["counts"]["collapsed"],
+                                     w["mean"], w["std"], w["min"], w["max"]))
+    if res["windows"]:
+        print("flows %.3f s  advection %.4f s  ftle %.4f s" % (res["time_flows_s"], res["time_advect_s"], res["time_ftle_s"]))
+    for path in (args.out, args.classes, args.json):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    if args.out:
+        np.save(args.out, res["ftle"].cpu().numpy())
+    if args.classes:
+        np.save(args.classes, res["cls"].cpu().numpy())
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(doc, f, indent=1)
+    return doc
+
+
+def main_rife(Model, nd, argv=None):
+    """flow2d / flow3d: windows over the steps m -> m+h (or back) of the final IFNet flows."""
+    args = check_args(_args(nd, "FTLE fields of the flows of a RIFE model", "rife").parse_args(argv))
+
+    def make_model():
+        m = Model(-1, device=torch.device("cuda"))
+        try:
+            m.load_model("flownet.pkl", args.model)
+        except FileNotFoundError:
+            print("no flownet.pkl under %s: using random-init weights" % args.model)
+        m.eval()
+        return lambda frames, pairs: flow_eval.rife_flows(m, frames, pairs, args.batch)
+
+    return run(args, nd, "rife", make_model)
+
+
+def main_upflow(make_net, argv=None):
+    """upflow: windows over the steps t -> t+gap through flow_f_out, or back through flow_b_out."""
+    args = check_args(_args(2, "FTLE fields of UPFlow's flows", "upflow").parse_args(argv))
+
+    def make_model():
+        net = make_net(args.model)
+        return lambda frames, pairs: flow_eval.upflow_flows(net, frames, pairs, args.batch)
+
+    return run(args, 2, "upflow", make_model)

@@ -2816,6 +2816,146 @@ def advect(pos, flows, status=None, steps=None, method="euler", substeps=1, scal
 
 
 # --------------------------------------------------------------------------------------------
+# FTLE: the flow map of lattice seeds differentiated and reduced to Lyapunov exponents (fs_ftle{2,3}d)
+# --------------------------------------------------------------------------------------------
+FTLE_NOT_VALID, FTLE_OK, FTLE_ENDED, FTLE_NONFINITE, FTLE_COLLAPSED = 0, 1, 2, 3, 4  # FS_FTLE_*: class codes
+FTLE_K = 9  # FS_FTLE_K: the five class counts, then sum, sum of squares, minimum and maximum of the stored FTLE
+FTLE_CLASSES = ("not_valid", "ok", "ended", "nonfinite", "collapsed")
+
+
+def _lattice(lattice):
+    lattice = tuple(int(s) for s in lattice)
+    if len(lattice) not in (2, 3) or min(lattice) < 2:
+        raise ValueError("lattice must be (Gh,Gw) or (Gd,Gh,Gw) with every extent >= 2, got %r" % (lattice,))
+    P = 1
+    for s in lattice:
+        P *= s
+    if P > 2 ** 31 - 1:
+        raise ValueError("a lattice holds at most 2^31 - 1 nodes, got %r" % (lattice,))
+    return lattice, P
+
+
+def ftle_cost(lattice, with_cg=False):
+    """(HBM bytes, flops) the algorithm needs for one ftle call on a lattice (Gh,Gw) or (Gd,Gh,Gw): the C map planes and
+    the status read once (neighbours come from the cache), the fp32 exponent and the uint8 class written, with_cg the
+    C (C + 1) / 2 tensor planes too.  Flops per node: 2 per entry of J, 2 C - 1 per entry of G, ~30 for the logarithm,
+    ~10 for the 2-D closed form or ~45 per Jacobi rotation at a nominal two sweeps of three in 3-D."""
+    lattice, P = _lattice(lattice)
+    C = len(lattice)
+    NG = C * (C + 1) // 2
+    nbytes = P * (4 * C + 1 + 5 + (4 * NG if with_cg else 0))
+    flops = P * (2 * C * C + NG * (2 * C - 1) + 30 + (10 if C == 2 else 2 * 3 * 45))
+    return nbytes, flops
+
+
+def lattice_seeds(shape, refine=1, device="cuda"):
+    """(seeds [C,P] fp32, lattice extents, spacing) of the lattice that refines a grid of spatial `shape` ((H,W) or
+    (D,H,W)) `refine` times: (S_c - 1) * refine + 1 nodes per axis at the fp32 of i / refine, x fastest (component 0
+    is x, along W, as grid_seeds has it); the extents come slowest first, as `shape` does; spacing = 1 / refine in
+    elements.  What ops.advect returns for these seeds is the flow map ops.ftle differentiates."""
+    shape = tuple(int(s) for s in shape)
+    refine = int(refine)
+    if len(shape) not in (2, 3) or min(shape) < 2:
+        raise ValueError("shape must be (H,W) or (D,H,W) with every extent >= 2, got %r" % (shape,))
+    if refine < 1:
+        raise ValueError("refine must be >= 1, got %d" % refine)
+    lattice = tuple((s - 1) * refine + 1 for s in shape)
+    _lattice(lattice)
+    axes = [(torch.arange(n, dtype=torch.float64, device=device) / refine).to(torch.float32) for n in lattice]
+    mesh = torch.meshgrid(*axes, indexing="ij")
+    return torch.stack([m.reshape(-1) for m in mesh[::-1]], 0).contiguous(), lattice, 1.0 / refine
+
+
+def ftle(pos, status, lattice, spacing, T, valid=None, accept_out=False, with_cg=False, summary=True):
+    """Finite-time Lyapunov exponents of a flow map sampled on a lattice, one launch (fs_ftle{2,3}d).
+
+    pos: [C,P] fp32 on a GPU, the end positions ops.advect returns for lattice_seeds (component 0 = x); rows may be
+    strided (a [C,P] slice of a recorded trajectory passes as it is), elements of a row are contiguous.  status: uint8
+    [P], advect's.  lattice: (Gh,Gw) or (Gd,Gh,Gw) with P nodes, x fastest.  spacing: the seed spacing in elements, one
+    value or one per lattice axis (in the lattice's order).  T: the integration time; only |T| enters.  valid: optional
+    bool / uint8 [P] or [*lattice]; nodes outside it get class FTLE_NOT_VALID (they still serve as neighbours).
+    accept_out: particles that left the box count with their exit point instead of ending their neighbourhood.
+
+    Per node the map is differentiated along every axis by a central difference where both neighbours are usable, a
+    one-sided one where only one is, in fp64; G = J^T J; ftle = ln(sqrt(lambda_max(G))) / |T|, stored as fp32
+    (include/flowsci_hip.h states the order of operations; tests/ftle_ref.py restates it).  Classes: FTLE_OK,
+    FTLE_ENDED (no difference along some axis), FTLE_NONFINITE (a used map value or the result is not finite),
+    FTLE_COLLAPSED (lambda_max == 0); ftle is NaN off FTLE_OK.
+
+    Returns a dict: ftle (fp32 [*lattice]), cls (uint8 [*lattice]); with_cg: cg (fp32 [C(C+1)/2, *lattice], planes xx,
+    xy, yy, xz, yz, zz; NaN off OK and COLLAPSED); summary: summary (fp64 [FTLE_K] on the device: the five class
+    counts, then sum, sum of squares, minimum and maximum of the stored ftle over the OK nodes -- ftle_stats reads it).
+    Never synchronises.  A measurement on detached values: nothing is differentiated."""
+    lattice, P = _lattice(lattice)
+    nd = len(lattice)
+    try:
+        hs = [float(v) for v in spacing] if hasattr(spacing, "__len__") else [float(spacing)] * nd
+    except TypeError:
+        raise ValueError("spacing must be a number or one per lattice axis, got %r" % (spacing,))
+    if len(hs) != nd or not all(0 < h < float("inf") for h in hs):
+        raise ValueError("spacing must be one or %d finite positive values, got %r" % (nd, spacing))
+    T = abs(float(T))
+    if not (0 < T < float("inf")):
+        raise ValueError("T must be finite and non-zero, got %r" % (T,))
+    if not isinstance(pos, torch.Tensor) or not isinstance(status, torch.Tensor):
+        raise ValueError("pos and status must be tensors")
+    if not pos.is_cuda:
+        raise ValueError("pos must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (pos.device,))
+    dev = pos.device
+    if pos.dim() != 2 or tuple(pos.shape) != (nd, P):
+        raise ValueError("pos must be [%d,%d] for the lattice %s, got shape %s" % (nd, P, lattice, tuple(pos.shape)))
+    if status.dtype != torch.uint8 or status.numel() != P or status.device != dev:
+        raise ValueError("status must be a uint8 tensor of %d elements on %s, got %s %s on %s" % (
+            P, dev, status.dtype, tuple(status.shape), status.device))
+    pos = pos.detach()
+    if pos.dtype != torch.float32:
+        pos = pos.to(torch.float32)
+    if pos.stride(1) != 1 or pos.stride(0) < P:
+        pos = pos.contiguous()
+    status = status.reshape(-1).contiguous()
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or valid.numel() != P:
+            raise ValueError("valid must be a bool / uint8 tensor of %d elements or None" % P)
+        if valid.device != dev:
+            raise ValueError("valid must be on pos's device %s, got %s" % (dev, valid.device))
+        valid = valid.reshape(-1).to(torch.uint8).contiguous()
+    out = {"ftle": torch.empty(lattice, dtype=torch.float32, device=dev),
+           "cls": torch.empty(lattice, dtype=torch.uint8, device=dev)}
+    if with_cg:
+        out["cg"] = torch.empty((nd * (nd + 1) // 2,) + lattice, dtype=torch.float32, device=dev)
+    ws = None
+    if summary:
+        lib = _lib.lib()
+        nb = getattr(lib, "fs_ftle%dd_ws_bytes" % nd)(nd, *lattice)
+        if nb < 0:
+            _lib.check(int(-nb), "fs_ftle%dd_ws_bytes" % nd)
+        ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
+        out["summary"] = torch.empty(FTLE_K, dtype=torch.float64, device=dev)
+    # component 0 and axis 0 run along x: the lattice's last axis
+    inv_h = (ctypes.c_double * nd)(*[1.0 / h for h in hs[::-1]])
+    inv_2h = (ctypes.c_double * nd)(*[1.0 / (2.0 * h) for h in hs[::-1]])
+    nbytes, flops = ftle_cost(lattice, with_cg)
+    args = (pos.data_ptr(), pos.stride(0), status.data_ptr(), _ptr(valid), nd) + lattice + (
+        inv_h, inv_2h, 1.0 / T, int(bool(accept_out)), out["ftle"].data_ptr(), out["cls"].data_ptr(),
+        _ptr(out.get("cg")), _ptr(ws), _ptr(out.get("summary")), _stream(pos))
+    with torch.cuda.device(dev):
+        _call("fs_ftle%dd" % nd, *args, algo_bytes=nbytes, algo_flops=flops)
+    return out
+
+
+def ftle_stats(summary):
+    """A summary of ops.ftle as plain numbers (synchronises): {"counts": {class name: n}, "mean", "std", "min", "max"}
+    of the stored FTLE over the OK nodes; the four are NaN when there is none."""
+    s = [float(v) for v in summary.cpu().tolist()]
+    n = s[FTLE_OK]
+    nan = float("nan")
+    mean = s[5] / n if n else nan
+    var = max(0.0, s[6] / n - mean * mean) if n else nan
+    return {"counts": {name: int(s[k]) for k, name in enumerate(FTLE_CLASSES)}, "mean": mean,
+            "std": var ** 0.5 if n else nan, "min": s[7] if n else nan, "max": s[8] if n else nan}
+
+
+# --------------------------------------------------------------------------------------------
 # Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
 # --------------------------------------------------------------------------------------------
 import numpy as _np

@@ -23,8 +23,9 @@ With a known motion (--dataset or --gt) the same seeds are also advected through
 the report gains the per-step drift between the two trajectories: what the per-pair errors add up to (--map-out
 without --out records nothing per step: the drift after the last step only).
 
-Out of scope: FTLE and other derivatives of the flow map (--map-out writes the map they start from); batches of several
-series in one launch; interleaved ([*sp, C]) flow layouts; autograd through the op."""
+FTLE fields, the derivative of the flow map reduced to Lyapunov exponents, are opticalflowscivis_amd/ftle.py (the `ftle`
+entry points).  Out of scope: batches of several series in one launch; interleaved ([*sp, C]) flow layouts; autograd
+through the op."""
 import argparse
 import json
 import os
