@@ -53,8 +53,9 @@ enum {
  *   390  fs_series_encode / fs_series_encode_ws_bytes (padded fp32 planes back to a stored type: the inverse of the
  *        gather's decode, for writing rebuilt series and flows).
  *   400  fs_advect2d / fs_advect3d (pathlines: particles advected through consecutive displacement fields).
- *   410  fs_ftle2d / fs_ftle3d and their _ws_bytes queries (finite-time Lyapunov exponents of a lattice flow map). */
-#define FS_ABI_VERSION 410
+ *   410  fs_ftle2d / fs_ftle3d and their _ws_bytes queries (finite-time Lyapunov exponents of a lattice flow map).
+ *   420  fs_velgrad2d / fs_velgrad3d and their _ws_bytes queries (divergence, vorticity, Q and lambda2 of step flows). */
+#define FS_ABI_VERSION 420
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -853,6 +854,70 @@ int fs_ftle2d(const float* map, long long map_cstride, const unsigned char* stat
 int fs_ftle3d(const float* map, long long map_cstride, const unsigned char* status, const unsigned char* valid, int C,
               int Gd, int Gh, int Gw, const double* inv_h, const double* inv_2h, double inv_T, int accept_out,
               float* ftle, unsigned char* cls, float* cg, double* ws, double* out, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Velocity gradient -- divergence, vorticity, the Q criterion and lambda2 of K step flows, one launch (plus the
+ * summary's).
+ *   flows: K fields of C fp32 planes of D*H*W elements (2-D: D = 1, C = 2; 3-D: C = 3), planes of one field contiguous,
+ *     field k at + k * flow_sstride elements (>= C*D*H*W: every other field of a stack is read in place), node (z, y, x)
+ *     at (z * H + y) * W + x; displacements in elements, component 0 and axis 0 along x (W), 1 along y, 2 along z.
+ *   inv_h, inv_2h: HOST arrays of C doubles, 1 / h_c and 1 / (2 h_c) with h_c the node spacing along axis c.  scale: HOST
+ *     array of K doubles, the reciprocal of the time step k spans: velocity = displacement * scale[k].  The host forms
+ *     them in fp64 and the device divides nothing by them; the scales travel in the launch's arguments (steps beyond
+ *     FS_VG_STEPS_PER_LAUNCH = 256 go out in further launches of the same call).
+ *   fields: a bitmask of FS_VG_DIV, FS_VG_VORT, FS_VG_VMAG, FS_VG_Q, FS_VG_L2, FS_VG_J; NP = the number of planes it
+ *     selects, in this order: div (1), vort (2-D: 1, 3-D: 3), vmag (1), q (1), l2 (1), J (C*C, plane r * C + c).
+ *   Per node, in fp64 without fused multiply-adds (a restatement with the same operations in the same order reproduces
+ *   every bit of div, vort, q and J; tests/velgrad_ref.py):
+ *     The difference along axis c at index i: central where i-1 and i+1 exist, lo = i-1, hi = i+1, w = inv_2h[c]; else
+ *       forward where i+1 exists, lo = i, hi = i+1, w = inv_h[c]; else backward, lo = i-1, hi = i, w = inv_h[c].
+ *     J[r][c] = (((double)u_r[hi] - (double)u_r[lo]) * w) * scale[k]     (all C*C entries, whatever is selected)
+ *     div = (J00 + J11) + J22                                              (2-D: J00 + J11)
+ *     vort = (J21 - J12, J02 - J20, J10 - J01)                             (2-D: the scalar J10 - J01)
+ *     vmag = sqrt((vort0^2 + vort1^2) + vort2^2)                           (2-D: |vort|)
+ *     s_aa = J_aa; for a < b: s_ab = 0.5 (J_ab + J_ba), o_ab = 0.5 (J_ab - J_ba)      (S and Omega)
+ *     nS = ((s00^2 + s11^2) + s22^2) + 2 ((s01^2 + s02^2) + s12^2)          (2-D: (s00^2 + s11^2) + 2 s01^2)
+ *     nO = 2 ((o01^2 + o02^2) + o12^2)                                      (2-D: 2 o01^2)
+ *     q = 0.5 (nO - nS)
+ *     M = S^2 + Omega^2 (symmetric):
+ *       m00 = ((s00^2 + s01^2) + s02^2) - (o01^2 + o02^2)     m01 = ((s00 s01 + s01 s11) + s02 s12) - o02 o12
+ *       m11 = ((s01^2 + s11^2) + s12^2) - (o01^2 + o12^2)     m02 = ((s00 s02 + s01 s12) + s02 s22) + o01 o12
+ *       m22 = ((s02^2 + s12^2) + s22^2) - (o02^2 + o12^2)     m12 = ((s01 s02 + s11 s12) + s12 s22) - o01 o02
+ *       (2-D: m00 = (s00^2 + s01^2) - o01^2, m11 = (s01^2 + s11^2) - o01^2, m01 = s00 s01 + s01 s11)
+ *     l2 = the median eigenvalue of M.  3-D: cyclic Jacobi rotations on M scaled by the power of two that brings its
+ *       largest entry magnitude into [0.5, 1), until the off-diagonal entries sum to at most 2^-45 (at most 10 sweeps),
+ *       then the median of the three diagonal entries, scaled back: every eigenvalue is within 2^-44 ||M||_F of one of
+ *       them, and a diagonal M comes back untouched (a constant field gives exactly 0, a rigid rotation exactly
+ *       -|rate|^2).  2-D: the median of 0 and the two eigenvalues 0.5 (m00 + m11) -+ sqrt((0.5 (m00 - m11))^2 + m01^2) --
+ *       the planar field embedded in 3-D.  trace M = -2 q.
+ *     Each selected value is rounded to fp32 once.  The node is NOT FINITE when an entry of J or a selected value (after
+ *     its rounding) is not finite; every selected plane of the node is then NaN.
+ *   out: fp32 [K][NP][D*H*W], contiguous.
+ *   flags: uint8 [K][D*H*W] or NULL.  bit 0: q is selected and the stored q > 0; bit 1: l2 is selected and the stored
+ *     l2 < 0; bit 7: the node is not finite (bits 0-1 are then clear).
+ *   summary: fp64 [K][FS_VG_K] or NULL, per step: 0 the nodes that are not finite, 1 those with bit 0, 2 those with bit 1,
+ *     3 those with both; then for each of div, vmag, q, l2 (in this order, at 4 + 4 n) the sum, the sum of squares, the
+ *     minimum (+inf when none) and the maximum (-inf when none) of the STORED fp32 values over the finite nodes.  What
+ *     depends on a field that is not selected is NaN.  Per-workgroup fp64 partials in `ws` (fs_velgrad{2,3}d_ws_bytes
+ *     bytes, 8-byte aligned; needed only with summary), combined by a second launch in a fixed order: bitwise
+ *     reproducible, no atomics; step k's numbers do not depend on K.
+ *   FS_ERR_NULLPTR: flows, inv_h, inv_2h, scale or out NULL, or summary without ws.  FS_ERR_SHAPE: C other than 2 (2-D) /
+ *   3 (3-D), an extent below 2, more than 2^31 - 1 nodes, flow_sstride below C*D*H*W.  FS_ERR_ARG: fields empty or with
+ *   unknown bits, K < 1, an inv_h[c], inv_2h[c] or scale[k] that is not finite or not positive.  All of them are returned
+ *   before anything is launched.  The _ws_bytes queries launch nothing and return the byte count or -(FS_ERR_*).
+ */
+enum { FS_VG_DIV = 1, FS_VG_VORT = 2, FS_VG_VMAG = 4, FS_VG_Q = 8, FS_VG_L2 = 16, FS_VG_J = 32, FS_VG_ALL = 63 };
+enum { FS_VG_FLAG_Q = 1, FS_VG_FLAG_L2 = 2, FS_VG_FLAG_NONFINITE = 128 };
+#define FS_VG_K 20
+#define FS_VG_STEPS_PER_LAUNCH 256
+long long fs_velgrad2d_ws_bytes(int K, int C, int H, int W);
+long long fs_velgrad3d_ws_bytes(int K, int C, int D, int H, int W);
+int fs_velgrad2d(const float* flows, int K, int C, int H, int W, long long flow_sstride, const double* inv_h,
+                 const double* inv_2h, const double* scale, unsigned fields, float* out, unsigned char* flags,
+                 double* ws, double* summary, fs_stream_t stream);
+int fs_velgrad3d(const float* flows, int K, int C, int D, int H, int W, long long flow_sstride, const double* inv_h,
+                 const double* inv_2h, const double* scale, unsigned fields, float* out, unsigned char* flags,
+                 double* ws, double* summary, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

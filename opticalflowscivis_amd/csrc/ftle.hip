@@ -20,6 +20,7 @@
 // each workgroup writes its FS_FTLE_K partials to `ws` ([K][G]) and a second launch combines the G partials in a fixed
 // order: no atomics, bitwise reproducible.
 #include "common.hpp"
+#include "jacobi3.hpp"
 
 namespace {
 
@@ -42,32 +43,6 @@ __device__ __forceinline__ bool usable(const unsigned char* __restrict__ st, siz
   return s == FS_ADV_ALIVE || (accept_out && s == FS_ADV_OUT);
 }
 
-// One Jacobi rotation in the (p, q) plane of a symmetric 3 x 3 matrix whose entries are at most 1 in magnitude; r is
-// the third index.  The angle is computed in fp32 (any angle keeps the eigenvalues as long as the rotation is
-// orthogonal; an angle good to 1e-7 leaves 1e-7 of a_pq behind, which the next sweep removes), c = 1 / sqrt(1 + t^2)
-// in fp64 from the fp32 estimate by two Newton steps, so c^2 + s^2 = 1 to fp64 rounding.  No fp64 division or sqrt;
-// |t| may exceed 1 by the estimate's rounding, which nothing below relies on.
-__device__ __forceinline__ void rotate(double& app, double& aqq, double& apq, double& arp, double& arq) {
-  if (!(fabs(apq) > 0x1p-60)) return;  // nothing to remove (and o * o below stays a normal fp32 number)
-  // the hardware's one-instruction sqrt / rcp / rsq (1 ulp, normal operands here): the angle needs no more
-  const float o = (float)apq, d = (float)(aqq - app);
-  const float h = __builtin_amdgcn_sqrtf(d * d + 4.f * (o * o));  // >= 2 |o| > 0
-  const float t32 = (2.f * o) * __builtin_amdgcn_rcpf(d + copysignf(h, d));  // the smaller root of t^2 + t d / o - 1 = 0
-  const double t = (double)t32;
-  const double x = 1.0 + t * t;
-  double c = (double)__builtin_amdgcn_rsqf((float)x);
-  c = c * (1.5 - (0.5 * x) * (c * c));
-  c = c * (1.5 - (0.5 * x) * (c * c));
-  const double s = t * c;
-  const double cc = c * c, ss = s * s, sc = s * c;
-  const double npp = (cc * app - (2.0 * sc) * apq) + ss * aqq;
-  const double nqq = (ss * app + (2.0 * sc) * apq) + cc * aqq;
-  const double npq = (cc - ss) * apq + sc * (app - aqq);
-  const double nrp = c * arp - s * arq;
-  const double nrq = s * arp + c * arq;
-  app = npp; aqq = nqq; apq = npq; arp = nrp; arq = nrq;
-}
-
 // Largest eigenvalue of the symmetric positive semi-definite g = (xx, xy, yy, xz, yz, zz): cyclic Jacobi on the matrix
 // scaled by a power of two (exact) to a trace in [0.5, 1), at most kSweeps sweeps, ended when the off-diagonal entries
 // sum to less than 2^-45 (every eigenvalue then lies within that of a diagonal entry, and lambda_max >= trace / 3: a
@@ -84,9 +59,9 @@ __device__ __forceinline__ double lmax3(const double (&g)[6]) {
   double a00 = g[0] * dn, a01 = g[1] * dn, a11 = g[2] * dn, a02 = g[3] * dn, a12 = g[4] * dn, a22 = g[5] * dn;
   for (int sw = 0; sw < kSweeps; ++sw) {
     if (!((fabs(a01) + fabs(a02)) + fabs(a12) > 0x1p-45)) break;
-    rotate(a00, a11, a01, a02, a12);
-    rotate(a00, a22, a02, a01, a12);
-    rotate(a11, a22, a12, a01, a02);
+    fs::jacobi_rotate(a00, a11, a01, a02, a12);
+    fs::jacobi_rotate(a00, a22, a02, a01, a12);
+    fs::jacobi_rotate(a11, a22, a12, a01, a02);
   }
   return ldexp(fmax(fmax(a00, a11), a22), e);
 }

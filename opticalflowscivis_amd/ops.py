@@ -2956,6 +2956,154 @@ def ftle_stats(summary):
 
 
 # --------------------------------------------------------------------------------------------
+# Velocity gradient: divergence, vorticity, Q and lambda2 of step flows (fs_velgrad{2,3}d)
+# --------------------------------------------------------------------------------------------
+VG_FIELDS = {"div": 1, "vort": 2, "vmag": 4, "q": 8, "l2": 16, "grad": 32}  # FS_VG_*: in the order of the planes
+VG_DEFAULT = ("div", "vmag", "q", "l2")
+VG_K = 20  # FS_VG_K: four counts, then sum / sum of squares / min / max of div, vmag, q and l2
+VG_FLAG_Q, VG_FLAG_L2, VG_FLAG_NONFINITE = 1, 2, 128  # FS_VG_FLAG_*
+_VG_STATS = ("div", "vmag", "q", "l2")  # the fields the summary covers, at 4 + 4 n
+
+
+def _vg_fields(fields):
+    """The bitmask of a field selection: names (a list, or comma-separated in a string), or the mask itself."""
+    if isinstance(fields, int) and not isinstance(fields, bool):
+        mask = fields
+    else:
+        names = [n.strip() for n in fields.split(",")] if isinstance(fields, str) else list(fields)
+        unknown = [n for n in names if n not in VG_FIELDS]
+        if unknown:
+            raise ValueError("unknown field(s) %r: choose among %s" % (unknown, ", ".join(VG_FIELDS)))
+        mask = 0
+        for n in names:
+            mask |= VG_FIELDS[n]
+    if mask <= 0 or mask & ~63:
+        raise ValueError("fields must select at least one of %s, got %r" % (", ".join(VG_FIELDS), fields))
+    return mask
+
+
+def velgrad_planes(fields, nd):
+    """name -> slice of the NP planes ops.velgrad writes for `fields` in nd dimensions, in the kernel's order: div (1),
+    vort (1 in 2-D, 3 in 3-D), vmag (1), q (1), l2 (1), grad (nd * nd, plane r * nd + c = d u_r / d x_c)."""
+    mask = _vg_fields(fields)
+    if nd not in (2, 3):
+        raise ValueError("nd must be 2 or 3, got %r" % (nd,))
+    width = {"div": 1, "vort": 3 if nd == 3 else 1, "vmag": 1, "q": 1, "l2": 1, "grad": nd * nd}
+    planes, p = {}, 0
+    for name, bit in VG_FIELDS.items():
+        if mask & bit:
+            planes[name] = slice(p, p + width[name])
+            p += width[name]
+    return planes
+
+
+def velgrad_cost(shape, K=1, fields=VG_DEFAULT, with_flags=True):
+    """(HBM bytes, flops) the algorithm needs for one velgrad call on K step flows of spatial `shape` ((H,W) or
+    (D,H,W)): the C planes read once (neighbours come from the cache), the NP selected planes and the flag byte
+    written: 4 C + 4 NP (+ 1) per node.  Flops per node: 3 per entry of J, C - 1 for div, C for vort, 2 C for vmag,
+    ~25 (3-D) / ~10 (2-D) for S, Omega and q, and for l2 ~45 for M plus ~45 per Jacobi rotation at a nominal two
+    sweeps of three in 3-D, ~15 for the closed form in 2-D."""
+    shape, P = _lattice(shape)
+    C = len(shape)
+    mask = _vg_fields(fields)
+    NP = sum(s.stop - s.start for s in velgrad_planes(mask, C).values())
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1, got %d" % K)
+    nbytes = K * P * (4 * C + 4 * NP + (1 if with_flags else 0))
+    per = 3 * C * C
+    per += (C - 1) if mask & 1 else 0
+    per += C if mask & 6 else 0
+    per += 2 * C if mask & 4 else 0
+    per += (25 if C == 3 else 10) if mask & 24 else 0
+    per += (45 + 2 * 3 * 45 if C == 3 else 15) if mask & 16 else 0
+    return nbytes, K * P * per
+
+
+def velgrad(flows, fields=VG_DEFAULT, spacing=1.0, scale=1.0, with_flags=True, summary=True):
+    """Divergence, vorticity, the Q criterion and lambda2 of K step flows, one launch (fs_velgrad{2,3}d).
+
+    flows: [K,2,H,W] or [K,3,D,H,W] fp32 displacements on a GPU, in elements, channel 0 along W; the step stride may be
+    anything (stack[1::2] is read in place).  fields: names out of div, vort, vmag, q, l2, grad (a list or a
+    comma-separated string).  spacing: the node spacing, one value or one per axis in the tensor's axis order
+    ((D,)H,W).  scale: the reciprocal of the time a step spans, one value or K: velocity = displacement * scale.
+
+    Per node the velocity is differentiated along every axis by a central difference where both neighbours exist, a
+    one-sided one at the border, in fp64: J[r][c] = d u_r / d x_c; div = tr J; vort = curl u (a scalar in 2-D), vmag
+    its magnitude; q = (||Omega||^2 - ||S||^2) / 2; l2 = the median eigenvalue of S^2 + Omega^2 (2-D: of the planar field
+    embedded in 3-D).  include/flowsci_hip.h states the order of operations; tests/velgrad_ref.py restates it and
+    agrees bit for bit on div, vort, q and grad.  A node at which a used value or a selected result is not finite is NaN
+    in every plane.
+
+    Returns a dict: out (fp32 [K,NP,*sp]), planes (name -> slice of the NP planes, velgrad_planes), with_flags: flags
+    (uint8 [K,*sp]: VG_FLAG_Q q > 0, VG_FLAG_L2 l2 < 0, VG_FLAG_NONFINITE), summary: summary (fp64 [K,VG_K] on the
+    device -- velgrad_stats reads it).  Never synchronises.  A measurement on detached values: nothing is
+    differentiated."""
+    mask = _vg_fields(fields)
+    flows, nd = _advect_flows(flows)
+    sp, P = _lattice(flows.shape[2:])
+    K = int(flows.shape[0])
+    try:
+        hs = [float(v) for v in spacing] if hasattr(spacing, "__len__") else [float(spacing)] * nd
+        ss = [float(v) for v in scale] if hasattr(scale, "__len__") else [float(scale)] * K
+    except TypeError:
+        raise ValueError("spacing and scale must be numbers or sequences of numbers, got %r and %r" % (spacing, scale))
+    if len(hs) != nd or not all(0 < h < float("inf") for h in hs):
+        raise ValueError("spacing must be one or %d finite positive values, got %r" % (nd, spacing))
+    if len(ss) != K or not all(0 < s < float("inf") for s in ss):
+        raise ValueError("scale must be one or %d finite positive values, got %r" % (K, scale))
+    dev = flows.device
+    planes = velgrad_planes(mask, nd)
+    NP = sum(s.stop - s.start for s in planes.values())
+    res = {"out": torch.empty((K, NP) + sp, dtype=torch.float32, device=dev), "planes": planes}
+    if with_flags:
+        res["flags"] = torch.empty((K,) + sp, dtype=torch.uint8, device=dev)
+    ws = None
+    if summary:
+        nb = getattr(_lib.lib(), "fs_velgrad%dd_ws_bytes" % nd)(K, nd, *sp)
+        if nb < 0:
+            _lib.check(int(-nb), "fs_velgrad%dd_ws_bytes" % nd)
+        ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
+        res["summary"] = torch.empty((K, VG_K), dtype=torch.float64, device=dev)
+    # component 0 and axis 0 run along x: the tensor's last axis
+    inv_h = (ctypes.c_double * nd)(*[1.0 / h for h in hs[::-1]])
+    inv_2h = (ctypes.c_double * nd)(*[1.0 / (2.0 * h) for h in hs[::-1]])
+    fss = flows.stride(0) if K > 1 else nd * P  # (a single field's step stride is never used)
+    nbytes, flops = velgrad_cost(sp, K, mask, with_flags)
+    args = (flows.data_ptr(), K, nd) + sp + (fss, inv_h, inv_2h, (ctypes.c_double * K)(*ss), mask,
+                                             res["out"].data_ptr(), _ptr(res.get("flags")), _ptr(ws),
+                                             _ptr(res.get("summary")), _stream(flows))
+    with torch.cuda.device(dev):
+        _call("fs_velgrad%dd" % nd, *args, algo_bytes=nbytes, algo_flops=flops)
+    return res
+
+
+def velgrad_stats(summary, nodes):
+    """The summary of ops.velgrad as plain numbers (synchronises): one dict per step with n_finite, n_nonfinite,
+    frac_q_pos, frac_l2_neg, frac_both (vortex volume fractions of the `nodes` nodes of a step), rms_div, enstrophy (the
+    mean of vmag^2 / 2) and, per field of div, vmag, q, l2, NAME_mean, NAME_std, NAME_min, NAME_max over the finite
+    nodes.  What depends on a field that was not selected, or on finite nodes when there is none, is NaN."""
+    rows = summary.cpu().tolist()
+    nodes = int(nodes)
+    nan = float("nan")
+    out = []
+    for s in (rows if summary.dim() == 2 else [rows]):
+        n = nodes - int(s[0])
+        r = {"n_finite": n, "n_nonfinite": int(s[0]), "frac_q_pos": s[1] / nodes, "frac_l2_neg": s[2] / nodes,
+             "frac_both": s[3] / nodes}
+        for i, name in enumerate(_VG_STATS):
+            s1, s2, mn, mx = s[4 + 4 * i:8 + 4 * i]
+            mean = s1 / n if n else nan
+            var = max(0.0, s2 / n - mean * mean) if n and s2 == s2 else nan
+            r.update({name + "_mean": mean, name + "_std": var ** 0.5, name + "_min": mn if n else nan,
+                      name + "_max": mx if n else nan})
+        r["rms_div"] = (s[5] / n) ** 0.5 if n else nan
+        r["enstrophy"] = 0.5 * s[9] / n if n else nan
+        out.append(r)
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
 # --------------------------------------------------------------------------------------------
 import numpy as _np
