@@ -32,9 +32,10 @@ What reading the dispatch code against its operands decided (the rows pin each o
     staging loops, float atomics), so the vector forms stay correct -- rows "... misaligned, not inspected".
   * downsample3d_impl's `(Hin * Win) % 4` cannot fail once `Win % 4 == 0` holds, so it has no far side.
 
-Out of scope here (the next ledgers): warp2d.hip, laplacian*.hip, census3d.hip, flowsmooth3d.hip and the metrics sources
-(metrics.hip, flowmetrics.hip, series.hip).  losses.hip, wssim.hip, epilogue.hip and prelu.hip have theirs:
-tests/loss_ledger.py; corr2d.hip and corr3d.hip (both over corr_q.hpp) theirs: tests/corr_ledger.py."""
+Out of scope here (the next ledgers): census3d.hip, flowsmooth3d.hip and the metrics sources (metrics.hip, flowmetrics.hip,
+series.hip).  losses.hip, wssim.hip, epilogue.hip and prelu.hip have theirs: tests/loss_ledger.py; corr2d.hip and corr3d.hip
+(both over corr_q.hpp) theirs: tests/corr_ledger.py; warp2d.hip, laplacian.hip and laplacian3d.hip theirs:
+tests/w2lap_ledger.py."""
 from ledger_harness import normalize as _normalize
 
 ROWS = []
