@@ -54,8 +54,10 @@ enum {
  *        gather's decode, for writing rebuilt series and flows).
  *   400  fs_advect2d / fs_advect3d (pathlines: particles advected through consecutive displacement fields).
  *   410  fs_ftle2d / fs_ftle3d and their _ws_bytes queries (finite-time Lyapunov exponents of a lattice flow map).
- *   420  fs_velgrad2d / fs_velgrad3d and their _ws_bytes queries (divergence, vorticity, Q and lambda2 of step flows). */
-#define FS_ABI_VERSION 420
+ *   420  fs_velgrad2d / fs_velgrad3d and their _ws_bytes queries (divergence, vorticity, Q and lambda2 of step flows).
+ *   430  fs_label_regions2d / fs_label_regions3d and their _ws_bytes queries, fs_region_stats2d / fs_region_stats3d,
+ *        fs_region_follow2d / fs_region_follow3d (connected regions of flag maps, their table, where the flow carries them). */
+#define FS_ABI_VERSION 430
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -918,6 +920,77 @@ int fs_velgrad2d(const float* flows, int K, int C, int H, int W, long long flow_
 int fs_velgrad3d(const float* flows, int K, int C, int D, int H, int W, long long flow_sstride, const double* inv_h,
                  const double* inv_2h, const double* scale, unsigned fields, float* out, unsigned char* flags,
                  double* ws, double* summary, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Regions -- connected components of K flag maps, one table row per region, and the label every foreground node is
+ * carried onto by the step flow to the next map.  Node (z, y, x) of a step at (z * H + y) * W + x (2-D: D = 1); a step
+ * holds fewer than 2^31 - 1 nodes, every extent >= 1 (FS_ERR_SHAPE otherwise).
+ *
+ * fs_label_regions{2,3}d
+ *   mask: uint8, step k at + k * mask_sstride elements (>= D*H*W: every other map of a stack is read in place).  A node
+ *     is FOREGROUND iff (m & require) == require && (m & reject) == 0  (require, reject in 0..255).
+ *   conn: 0 = face neighbours (4 / 6), 1 = the full neighbourhood (8 / 26); anything else FS_ERR_ARG.
+ *   labels: int32 [K][D*H*W].  Background 0; a foreground node's label is 1 + the smallest linear index, within its own
+ *     step, of any node of its component.  Components never join across steps.  The definition does not depend on the
+ *     order of merges: the result is bitwise reproducible.
+ *   n_regions: int32 [K], the nodes of step k with labels == index + 1.  status: int32 [1], 0, or bit 0 set when a
+ *     find / union loop ran into its iteration cap (it cannot while parents strictly decrease; the cap keeps a bug from
+ *     spinning).  Both are zeroed by the call.
+ *   ws: fs_label_regions{2,3}d_ws_bytes bytes (the int32 parent array).
+ *   Three launches per FS_REGION_STEPS_PER_LAUNCH steps: tiles of FS_REGION_TILE* nodes are labelled in LDS by union-find
+ *   (parent < child); foreground nodes on tile faces unite with their earlier neighbours in other tiles through
+ *   agent-scope atomics (relaxed load, fetch-min) only; every node follows its parents and writes root + 1 to `labels`.
+ *   FS_ERR_NULLPTR: any pointer NULL.  FS_ERR_ARG: conn, K < 1, require / reject outside 0..255.
+ *
+ * fs_region_stats{2,3}d
+ *   labels as above (K <= FS_REGION_STEPS_PER_LAUNCH); rank: int32 [K][D*H*W], at the root node of a region (index
+ *   label - 1) its dense id within the step, 0 .. R_k - 1, in increasing label order; offsets: int64 [K+1] in DEVICE
+ *   memory, the prefix sums of R_k; R = offsets[K].  weights: fp32 [K][F][D*H*W] or NULL with F = 0; F <= 8.
+ *   Row offsets[k] + rank of every region:  count int64 [R];  coord_sum int64 [R][nd], the sums of the integer node
+ *   coordinates in the tensor's axis order ((z,) y, x);  bbox int32 [R][2][nd], inclusive minimum and maximum;  with
+ *   weights wsum fp64 [R][F] (fp64 atomic adds: the order is not fixed, the error is bounded by (n - 1) 2^-53 sum |w|),
+ *   wmin / wmax fp32 [R][F] (exact; reduced throughout as the order-preserving integer image of fp32, in which -0 < +0).  All outputs are initialised by the call.  A node whose label, rank or offsets do
+ *   not name a row of the table is skipped, never written through.  Weights must be finite on foreground nodes (not
+ *   checked).  Runs of equal row along x are reduced in the wave before one lane issues the run's atomics.
+ *   FS_ERR_ARG: K, F, R out of range.  R == 0: nothing launched.
+ *
+ * fs_region_follow{2,3}d
+ *   labels int32 [K][D*H*W], K >= 2; flows: fp32, step j at + j * flow_sstride elements (>= C*D*H*W), C planes, component
+ *   0 along x (W); flow j lives on the grid of map j and points to map j + 1.  dst: int32 [K-1][D*H*W]:
+ *     0 where labels[j][x] == 0; else per axis a  r_a = rintf((float)x_a + u_a(x))  (one fp32 add, round half to even);
+ *     FS_REGION_OUT where some axis fails r_a >= 0 && r_a <= extent_a - 1 (compared as floats: NaN, +-inf and 1e30 fail);
+ *     else L = labels[j+1][r]: L where L > 0, FS_REGION_TO_BACKGROUND otherwise.
+ *   FS_ERR_SHAPE: C other than 2 (2-D) / 3 (3-D), flow_sstride below C*D*H*W, an extent above
+ *   FS_REGION_FOLLOW_MAX_EXTENT = 2^24 (beyond it extent - 1 need not be a float and the range test would not be exact).
+ *   FS_ERR_ARG: K < 2.
+ * All validation happens before anything is launched; the _ws_bytes queries launch nothing and return the byte count or
+ * -(FS_ERR_*).
+ */
+#define FS_REGION_TILE2_H 32
+#define FS_REGION_TILE2_W 64
+#define FS_REGION_TILE3_D 8
+#define FS_REGION_TILE3_H 8
+#define FS_REGION_TILE3_W 32
+#define FS_REGION_MAX_WEIGHTS 8
+#define FS_REGION_STEPS_PER_LAUNCH 32768
+#define FS_REGION_FOLLOW_MAX_EXTENT 16777216
+enum { FS_REGION_OUT = -1, FS_REGION_TO_BACKGROUND = -2 };
+long long fs_label_regions2d_ws_bytes(int K, int H, int W);
+long long fs_label_regions3d_ws_bytes(int K, int D, int H, int W);
+int fs_label_regions2d(const unsigned char* mask, int K, int H, int W, long long mask_sstride, int require, int reject,
+                       int conn, int* labels, int* n_regions, int* status, int* ws, fs_stream_t stream);
+int fs_label_regions3d(const unsigned char* mask, int K, int D, int H, int W, long long mask_sstride, int require,
+                       int reject, int conn, int* labels, int* n_regions, int* status, int* ws, fs_stream_t stream);
+int fs_region_stats2d(const int* labels, const int* rank, const long long* offsets, const float* weights, int K, int F,
+                      int H, int W, long long R, long long* count, long long* coord_sum, int* bbox, double* wsum,
+                      float* wmin, float* wmax, fs_stream_t stream);
+int fs_region_stats3d(const int* labels, const int* rank, const long long* offsets, const float* weights, int K, int F,
+                      int D, int H, int W, long long R, long long* count, long long* coord_sum, int* bbox, double* wsum,
+                      float* wmin, float* wmax, fs_stream_t stream);
+int fs_region_follow2d(const int* labels, const float* flows, int K, int C, int H, int W, long long flow_sstride,
+                       int* dst, fs_stream_t stream);
+int fs_region_follow3d(const int* labels, const float* flows, int K, int C, int D, int H, int W, long long flow_sstride,
+                       int* dst, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

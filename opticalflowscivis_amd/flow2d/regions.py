@@ -1,0 +1,8 @@
+"""Vortex regions with the Flow-2D model: `python -m opticalflowscivis_amd.flow2d.regions --flows flows.npy --out labels.npy
+--track-ids tracks.npy --json report.json` labels the q > 0 (or l2 < 0) regions of every step flow (the model's, or given
+ones), measures them, links them along the flow and reports tracks and events; see opticalflowscivis_amd/regions.py."""
+from ..regions import main_rife
+from .model.RIFE import Model
+
+if __name__ == "__main__":
+    main_rife(Model, 2)

@@ -3104,6 +3104,278 @@ def velgrad_stats(summary, nodes):
 
 
 # --------------------------------------------------------------------------------------------
+# Regions: connected components of flag maps, their table, and where the flow carries them
+# (fs_label_regions{2,3}d, fs_region_stats{2,3}d, fs_region_follow{2,3}d)
+# --------------------------------------------------------------------------------------------
+REGION_TILE = {2: (32, 64), 3: (8, 8, 32)}  # FS_REGION_TILE*: the tile one workgroup labels in LDS
+REGION_OUT, REGION_TO_BACKGROUND = -1, -2   # FS_REGION_*: codes of fs_region_follow's dst
+REGION_MAX_WEIGHTS = 8                      # FS_REGION_MAX_WEIGHTS
+_REGION_CONN = {"face": 0, "full": 1}
+
+
+def _region_grid(sp):
+    sp = tuple(int(s) for s in sp)
+    P = 1
+    for s in sp:
+        P *= s
+    if len(sp) not in (2, 3) or min(sp) < 1:
+        raise ValueError("a region grid is (H,W) or (D,H,W) with every extent >= 1, got %r" % (sp,))
+    if P >= 2 ** 31 - 1:
+        raise ValueError("a step holds fewer than 2^31 - 1 nodes, got %r" % (sp,))
+    return sp, P
+
+
+def regions_cost(shape, K=1, op="label", F=0, fg_fraction=1.0):
+    """(HBM bytes, flops) the algorithm needs for one call of a region op ("label", "stats" or "follow") on K maps of
+    spatial `shape`.  label: the mask byte read and the label written per node (the parent array's traffic between the
+    launches is the algorithm's own, not compulsory).  stats: the label and F weights read per node.  follow (K - 1
+    steps): the label and the C flow planes read and dst written per node, one gathered label per foreground node
+    (fg_fraction of them).  The work is integer work: flops 0."""
+    sp, P = _region_grid(shape)
+    C = len(sp)
+    K, F = int(K), int(F)
+    if K < 1 or not 0 <= F <= REGION_MAX_WEIGHTS:
+        raise ValueError("K must be >= 1 and F in 0..%d, got %d and %d" % (REGION_MAX_WEIGHTS, K, F))
+    if op == "label":
+        return K * P * (1 + 4), 0
+    if op == "stats":
+        return K * P * (4 + 4 * F), 0
+    if op == "follow":
+        return max(0, K - 1) * (P * (4 + 4 * C + 4) + 4 * int(round(float(fg_fraction) * P))), 0
+    raise ValueError("op must be 'label', 'stats' or 'follow', got %r" % (op,))
+
+
+def label_regions(mask, require=VG_FLAG_Q, reject=VG_FLAG_NONFINITE, connectivity="face"):
+    """Connected components of K flag maps in one call (fs_label_regions{2,3}d).
+
+    mask: uint8 [K,H,W] or [K,D,H,W] on a GPU; the step stride may be anything (mask[1::2] is read in place).  A node is
+    foreground iff (m & require) == require and (m & reject) == 0: with the defaults ops.velgrad's flags go in as they
+    are (q > 0 and finite).  connectivity: "face" (4 / 6 neighbours) or "full" (8 / 26).
+
+    Returns a dict on the device: labels (int32 [K,*sp]; background 0, a foreground node carries 1 + the smallest linear
+    index, within its step, of any node of its component: the result does not depend on the order of merges),
+    n_regions (int32 [K]) and status (int32 [1]: 0, or bit 0 when a loop ran into its iteration cap -- region_table
+    checks it).  Never synchronises."""
+    if not isinstance(mask, torch.Tensor):
+        raise ValueError("mask must be a tensor")
+    if not mask.is_cuda:
+        raise ValueError("mask must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (mask.device,))
+    if mask.dtype != torch.uint8 or mask.dim() not in (3, 4):
+        raise ValueError("mask must be uint8 [K,H,W] or [K,D,H,W], got %s %s" % (mask.dtype, tuple(mask.shape)))
+    if min(mask.shape) < 1:
+        raise ValueError("mask must have no empty axis, got shape %s" % (tuple(mask.shape),))
+    if connectivity not in _REGION_CONN:
+        raise ValueError("connectivity must be 'face' or 'full', got %r" % (connectivity,))
+    require, reject = int(require), int(reject)
+    if not (0 <= require <= 255 and 0 <= reject <= 255):
+        raise ValueError("require and reject are bytes, got %r and %r" % (require, reject))
+    sp, P = _region_grid(mask.shape[1:])
+    nd = len(sp)
+    K = int(mask.shape[0])
+    mask = mask.detach()
+    if not mask[0].is_contiguous() or (K > 1 and mask.stride(0) < P):
+        mask = mask.contiguous()
+    dev = mask.device
+    res = {"labels": torch.empty((K,) + sp, dtype=torch.int32, device=dev),
+           "n_regions": torch.empty(K, dtype=torch.int32, device=dev),
+           "status": torch.empty(1, dtype=torch.int32, device=dev)}
+    nb = getattr(_lib.lib(), "fs_label_regions%dd_ws_bytes" % nd)(K, *sp)
+    if nb < 0:
+        _lib.check(int(-nb), "fs_label_regions%dd_ws_bytes" % nd)
+    ws = torch.empty((nb + 3) // 4, dtype=torch.int32, device=dev)
+    nbytes, flops = regions_cost(sp, K, "label")
+    with torch.cuda.device(dev):
+        _call("fs_label_regions%dd" % nd, mask.data_ptr(), K, *sp, mask.stride(0) if K > 1 else P, require, reject,
+              _REGION_CONN[connectivity], res["labels"].data_ptr(), res["n_regions"].data_ptr(),
+              res["status"].data_ptr(), ws.data_ptr(), _stream(mask), algo_bytes=nbytes, algo_flops=flops)
+    return res
+
+
+def _region_labels(labels):
+    """(labels tensor, status or None) of label_regions' dict or a bare int32 [K,*sp] GPU tensor."""
+    status = None
+    if isinstance(labels, dict):
+        labels, status = labels["labels"], labels.get("status")
+    if not isinstance(labels, torch.Tensor):
+        raise ValueError("labels must be a tensor or label_regions' result")
+    if not labels.is_cuda:
+        raise ValueError("labels must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (labels.device,))
+    if labels.dtype != torch.int32 or labels.dim() not in (3, 4) or min(labels.shape) < 1:
+        raise ValueError("labels must be int32 [K,H,W] or [K,D,H,W], got %s %s" % (labels.dtype, tuple(labels.shape)))
+    return labels.contiguous(), status
+
+
+def region_ranks(labels):
+    """(roots, rank, offsets) on the device, by a prefix sum over labels == index + 1 (plumbing: torch): roots bool
+    [K,P], rank int32 [K,*sp] -- at a root node its region's dense id within the step, in increasing label order --
+    and offsets int64 [K+1], the prefix sums of the regions per step.  Never synchronises."""
+    K = int(labels.shape[0])
+    P = labels[0].numel()
+    roots = labels.view(K, P) == torch.arange(1, P + 1, dtype=torch.int32, device=labels.device)
+    csum = torch.cumsum(roots, 1, dtype=torch.int32)
+    offsets = torch.zeros(K + 1, dtype=torch.int64, device=labels.device)
+    offsets[1:] = torch.cumsum(csum[:, -1].to(torch.int64), 0)
+    return roots, (csum - 1).view(labels.shape), offsets
+
+
+def region_stats(labels, rank, offsets, R, weights=None):
+    """The launch behind region_table (fs_region_stats{2,3}d), on device tensors and without a synchronisation: labels
+    int32 [K,*sp], rank int32 [K,*sp] (the dense id at every root node), offsets int64 [K+1] on the device, R their last
+    entry as a host int, weights fp32 [K,F,*sp] or None.  Returns count (int64 [R]), coord_sum (int64 [R,nd]), bbox (int32
+    [R,2,nd]), wsum (fp64 [R,F]), wmin, wmax (fp32 [R,F]) on the device."""
+    K, sp = int(labels.shape[0]), tuple(int(s) for s in labels.shape[1:])
+    nd = len(sp)
+    dev = labels.device
+    F = 0 if weights is None else int(weights.shape[1])
+    R = int(R)
+    count = torch.empty(R, dtype=torch.int64, device=dev)
+    coord = torch.empty((R, nd), dtype=torch.int64, device=dev)
+    bbox = torch.empty((R, 2, nd), dtype=torch.int32, device=dev)
+    wsum = torch.empty((R, F), dtype=torch.float64, device=dev)
+    wmin = torch.empty((R, F), dtype=torch.float32, device=dev)
+    wmax = torch.empty((R, F), dtype=torch.float32, device=dev)
+    nbytes, flops = regions_cost(sp, K, "stats", F)
+    if R > 0:
+        with torch.cuda.device(dev):
+            _call("fs_region_stats%dd" % nd, labels.data_ptr(), rank.data_ptr(), offsets.data_ptr(), _ptr(weights), K, F,
+                  *sp, R, count.data_ptr(), coord.data_ptr(), bbox.data_ptr(), wsum.data_ptr(), wmin.data_ptr(),
+                  wmax.data_ptr(), _stream(labels), algo_bytes=nbytes, algo_flops=flops)
+    return count, coord, bbox, wsum, wmin, wmax
+
+
+def region_table(labels, weights=None, names=None):
+    """One row per region of K label maps (fs_region_stats{2,3}d).
+
+    labels: label_regions' result (its status is checked: FlowsciKernelError when set) or its int32 labels.  weights:
+    optional fp32 [K,F,*sp] on the same device, F <= 8, finite on foreground nodes (ops.velgrad's planes are, under the
+    default reject bit); names: F names for the columns (default w0, w1, ...).
+
+    The number of rows R depends on the data, so this SYNCHRONISES: once, to learn the regions' offsets (and the status);
+    the finished rows then come to the host in one integer transfer (and one floating-point one with weights).  Ranking the roots is a prefix sum over
+    labels == index + 1 (torch); everything per node is the kernel's.
+
+    Returns host numpy arrays over the R rows, step by step in increasing label order: step, label (int32), count
+    (int64), centroid (fp64 [R,nd], exact: integer sums / count), bbox (int32 [R,2,nd], inclusive), per weight
+    NAME_sum, NAME_mean (fp64), NAME_min, NAME_max (fp32); offsets (int64 [K+1]: rows offsets[k] .. offsets[k+1] are
+    step k's); and rank, the int32 [K,*sp] DEVICE tensor of dense ids at root nodes, for region_links."""
+    labels, status = _region_labels(labels)
+    K, sp = int(labels.shape[0]), tuple(int(s) for s in labels.shape[1:])
+    sp, P = _region_grid(sp)
+    nd = len(sp)
+    dev = labels.device
+    F = 0
+    if weights is not None:
+        weights = _need_cuda_f32("weights", weights, nd + 2)
+        F = int(weights.shape[1])
+        if tuple(weights.shape) != (K, F) + sp or not 1 <= F <= REGION_MAX_WEIGHTS or weights.device != dev:
+            raise ValueError("weights must be [K,F,*sp] = [%d, 1..%d, %s] on %s, got %s on %s" %
+                             (K, REGION_MAX_WEIGHTS, sp, dev, tuple(weights.shape), weights.device))
+    names = ["w%d" % i for i in range(F)] if names is None else [str(n) for n in names]
+    if len(names) != F or len(set(names)) != F:
+        raise ValueError("names must be %d distinct names, got %r" % (F, names))
+    roots, rank, offsets = region_ranks(labels)
+    head = torch.cat([offsets, (status if status is not None else offsets[:1]).to(torch.int64).view(-1)[:1]]).cpu()
+    if status is not None and int(head[-1]) != 0:
+        raise _lib.FlowsciKernelError("fs_label_regions: a union-find loop ran into its iteration cap (status %d)"
+                                      % int(head[-1]))
+    off = head[:K + 1].numpy().copy()
+    R = int(off[-1])
+    count, coord, bbox, wsum, wmin, wmax = region_stats(labels, rank, offsets, R, weights)
+    # every region's label, scattered to its row from its root node (the other nodes write a spare row): no second sync
+    rows = torch.where(roots, offsets[:K, None] + rank.view(K, P), R)
+    label = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    label.scatter_(0, rows.view(-1), torch.arange(1, P + 1, dtype=torch.int32, device=dev).expand(K, P).reshape(-1))
+    del rows
+    ints = torch.cat([count, coord.reshape(-1), bbox.reshape(-1).to(torch.int64),
+                      label[:R].to(torch.int64)]).cpu().numpy()  # one transfer
+    cnt = ints[:R].copy()
+    c1, c2 = R + R * nd, R + 3 * R * nd
+    tab = {"step": _np.repeat(_np.arange(K, dtype=_np.int32), _np.diff(off)), "label": ints[c2:].astype(_np.int32),
+           "count": cnt, "centroid": ints[R:c1].reshape(R, nd).astype(_np.float64) / _np.maximum(cnt, 1)[:, None],
+           "bbox": ints[c1:c2].reshape(R, 2, nd).astype(_np.int32), "offsets": off, "rank": rank}
+    if F:
+        flo = torch.cat([wsum.reshape(-1), wmin.reshape(-1).double(), wmax.reshape(-1).double()]).cpu().numpy()  # fp32 -> fp64 is exact
+        ws_ = flo[:R * F].reshape(R, F)
+        mn_, mx_ = (flo[i * R * F:(i + 1) * R * F].reshape(R, F).astype(_np.float32) for i in (1, 2))
+        for i, n in enumerate(names):
+            tab[n + "_sum"] = ws_[:, i].copy()
+            tab[n + "_mean"] = ws_[:, i] / _np.maximum(cnt, 1)
+            tab[n + "_min"] = mn_[:, i].copy()
+            tab[n + "_max"] = mx_[:, i].copy()
+    return tab
+
+
+def region_follow(labels, flows):
+    """dst (int32 [K-1,*sp] on the device) of fs_region_follow{2,3}d: for every foreground node of map j the label of map
+    j + 1 its step flow carries it onto (x + u(x) in fp32, rounded half to even), REGION_OUT (-1) when that leaves the
+    grid or is not finite, REGION_TO_BACKGROUND (-2) when it lands on background; 0 on background.  flows: [K-1 or
+    more, C, *sp] fp32, channel 0 along W, any step stride.  Never synchronises."""
+    labels, _ = _region_labels(labels)
+    K, sp = int(labels.shape[0]), tuple(int(s) for s in labels.shape[1:])
+    sp, P = _region_grid(sp)
+    nd = len(sp)
+    if K < 2:
+        raise ValueError("following needs at least two label maps, got %d" % K)
+    if not isinstance(flows, torch.Tensor) or flows.dim() != nd + 2 or flows.shape[0] < K - 1 or \
+            tuple(flows.shape[2:]) != sp:
+        raise ValueError("flows must be [>= %d, %d, %s], got %s" %
+                         (K - 1, nd, sp, tuple(flows.shape) if isinstance(flows, torch.Tensor) else type(flows).__name__))
+    flows = _flow_operand("flows", flows.detach(), nd)
+    if flows.device != labels.device:
+        raise ValueError("labels and flows must be on one device, got %s and %s" % (labels.device, flows.device))
+    dst = torch.empty((K - 1,) + sp, dtype=torch.int32, device=labels.device)
+    nbytes, flops = regions_cost(sp, K, "follow")
+    with torch.cuda.device(labels.device):
+        _call("fs_region_follow%dd" % nd, labels.data_ptr(), flows.data_ptr(), K, nd, *sp,
+              flows.stride(0) if flows.shape[0] > 1 else nd * P, dst.data_ptr(), _stream(labels), algo_bytes=nbytes,
+              algo_flops=flops)
+    return dst
+
+
+def region_links(labels, flows, table):
+    """Flow-guided links between consecutive label maps: fs_region_follow, then equal (source region, destination)
+    pairs counted on the device (integer plumbing: torch.unique over one int64 key per foreground node).
+
+    table: region_table's result for the same labels (its rank and offsets are used).  Returns a list with one dict of
+    host arrays per step pair j -> j + 1: src, dst (dense ids within their steps) and count (nodes of src carried onto
+    dst), and per source region of step j n_out (nodes leaving the grid) and n_to_background.  Synchronises."""
+    labels, _ = _region_labels(labels)
+    K = int(labels.shape[0])
+    P = labels[0].numel()
+    dst = region_follow(labels, flows).view(K - 1, P)
+    off = table["offsets"]
+    rank = table["rank"].view(K, P)
+    sizes = [int(off[k + 1] - off[k]) for k in range(K)]
+    M = max(sizes) + 2
+    if int(off[K]) * M >= 2 ** 63:  # the key below: (global row of the source) * M + destination code
+        raise ValueError("%d regions with up to %d per step overflow the 64-bit link key" % (int(off[K]), M - 2))
+    base = torch.from_numpy(_np.asarray(off[:K], dtype=_np.int64)).to(labels.device)
+    src_lab = labels.view(K, P)[:K - 1]
+    fg = src_lab > 0
+    jj, ii = fg.nonzero(as_tuple=True)
+    src = rank[jj, (src_lab[jj, ii] - 1).long()].long()
+    d = dst[jj, ii].long()
+    to = torch.where(d > 0, rank[jj + 1, (d - 1).clamp(min=0)].long() + 2, d + 2)  # 0: background, 1: out, 2 + id
+    keys, counts = torch.unique((base[jj] + src) * M + to, return_counts=True)
+    keys, counts = keys.cpu().numpy(), counts.cpu().numpy()
+    grow, kt = keys // M, keys % M
+    kj = _np.searchsorted(_np.asarray(off[1:K], dtype=_np.int64), grow, side="right")  # the step of a global row
+    ks = grow - _np.asarray(off, dtype=_np.int64)[kj]
+    out = []
+    for j in range(K - 1):
+        sel = kj == j
+        s, t, c = ks[sel], kt[sel], counts[sel]
+        n_out = _np.zeros(sizes[j], dtype=_np.int64)
+        n_bg = _np.zeros(sizes[j], dtype=_np.int64)
+        n_out[s[t == 1]] = c[t == 1]
+        n_bg[s[t == 0]] = c[t == 0]
+        lk = t >= 2
+        out.append({"src": s[lk].astype(_np.int64), "dst": (t[lk] - 2).astype(_np.int64), "count": c[lk].astype(_np.int64),
+                    "n_out": n_out, "n_to_background": n_bg})
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
 # --------------------------------------------------------------------------------------------
 import numpy as _np

@@ -17,8 +17,10 @@ Each chunk of step flows is estimated once, handed to one launch and dropped: de
 of results.  A step's scale is 1 / (frames it spans * --dt); --spacing is the node spacing, one value or one per axis
 ((D,)H,W).
 
-Out of scope: swirling strength and the Delta criterion; eigenvectors; vortex core lines and region labelling; a validity
-mask; autograd through the op; rendering."""
+Connected regions of the flag maps, their sizes and strengths, and their tracks through the series are
+opticalflowscivis_amd/regions.py (the `regions` entry points; --mask's file goes in there as it is).  Out of scope:
+swirling strength and the Delta criterion; eigenvectors; vortex core lines; a validity mask; autograd through the op;
+rendering."""
 import argparse
 import json
 import os
