@@ -56,8 +56,10 @@ enum {
  *   410  fs_ftle2d / fs_ftle3d and their _ws_bytes queries (finite-time Lyapunov exponents of a lattice flow map).
  *   420  fs_velgrad2d / fs_velgrad3d and their _ws_bytes queries (divergence, vorticity, Q and lambda2 of step flows).
  *   430  fs_label_regions2d / fs_label_regions3d and their _ws_bytes queries, fs_region_stats2d / fs_region_stats3d,
- *        fs_region_follow2d / fs_region_follow3d (connected regions of flag maps, their table, where the flow carries them). */
-#define FS_ABI_VERSION 430
+ *        fs_region_follow2d / fs_region_follow3d (connected regions of flag maps, their table, where the flow carries them).
+ *   440  fs_raycast3d / fs_raycast3d_ws_bytes, fs_brick_range3d (volumes to images: emission / absorption and maximum
+ *        intensity through a transfer function, with per-brick value ranges to jump over empty space). */
+#define FS_ABI_VERSION 440
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -991,6 +993,68 @@ int fs_region_follow2d(const int* labels, const float* flows, int K, int C, int 
                        int* dst, fs_stream_t stream);
 int fs_region_follow3d(const int* labels, const float* flows, int K, int C, int D, int H, int W, long long flow_sstride,
                        int* dst, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Ray casting -- K volumes through K cameras and one transfer function to K RGBA images, one launch (two with bricks).
+ *   volumes: K fp32 volumes of D*H*W nodes, node (z, y, x) at (z * H + y) * W + x, volume k at + k * sstride elements
+ *     (>= D*H*W: every other volume of a stack is read in place); every extent >= 2.  Axis 0 runs along x (W), 1 along
+ *     y, 2 along z; spacing: HOST array of 3 doubles, the node spacing along x, y, z; node i of axis a sits at i * h_a.
+ *   cameras: fp32 [K][18] in DEVICE memory, the 3-vectors o, ou, ov, d, du, dv in (x, y, z).  Pixel (i, j) -- column i
+ *     of row j of the image -- has the origin o + i ou + j ov and the direction normalize(d + i du + j dv)
+ *     (orthographic: du = dv = 0; perspective: ou = ov = 0).
+ *   tf: fp32 [n][4] RGBA in DEVICE memory, 16-byte aligned, 2 <= n <= FS_RC_MAX_TF, spread uniformly over [lo, hi];
+ *     finite, A >= 0 (not checked).
+ *   Per pixel, in fp32; the lines marked * without fused multiply-adds, in exactly this order, so that a restatement
+ *   (tests/raycast_ref.py) picks the same cell for every sample:
+ *   * O = (o + i ou) + j ov;  g = (d + i du) + j dv;  dir = g / sqrt((g_x^2 + g_y^2) + g_z^2)
+ *   * sample k = 0, 1, ...:  t = (k + 0.5) dt;  q_a = (O_a + t dir_a) * ih_a,  ih_a = fp32(1 / h_a)     (index position)
+ *     coverage  c = (c_x c_y) c_z,  c_a = max(0, 1 - max(0, max(-q_a, q_a - (N_a - 1))))
+ *     value     v = the trilinear sample at qc = min(max(q, 0), N - 1): cell i_a = min(floor(qc_a), N_a - 2), weight
+ *               f_a = qc_a - i_a; along x first (a + f_x (b - a)), then y, then z
+ *     position  u = min(max((v - lo) * fp32(1 / (hi - lo)), 0), 1);  table(u): s = u (n - 1), j = min(floor(s), n - 2),
+ *               row j + (s - j) (row j+1 - row j)
+ *     a sample whose v is not finite (a corner of its cell is NaN or +-inf) contributes nothing.
+ *     Every x + w (y - x) above (the interpolations, the table) and every C += w X below is one fused multiply-add;
+ *     nothing else is fused, so that the kernel with and without the brick map rounds alike.
+ *     FS_RC_DVR:  (R, G, B, A) = table(u);  e = exp(-((A c) dt));  C += T (1 - e) (R, G, B);  T *= e;  from C = 0, T = 1.
+ *                 The pixel is (C, 1 - T).  The ray ends after the first sample that leaves T < t_min (0: never).
+ *     FS_RC_MIP:  m = max(m, c u) from m = 0.  The pixel is table(m): a ray that meets nothing shows row 0.
+ *   The samples do not depend on where a ray meets the box.  The kernel bounds k by a slab test against the box grown
+ *   by one cell and a margin of 2^-15 of the coordinates' magnitude, plus one sample at either end; a sample outside
+ *   weighs c = 0 and changes nothing, visited or not.  A direction component of exactly 0 is legal; a ray with an
+ *   origin or direction that is not finite misses.  Sample indices end at 2^24 - 1.
+ *   image: fp32 [K][Hi][Wi][4], 16-byte aligned.  counts: int32 [K][Hi][Wi] or NULL, the samples the pixel gathered.
+ *
+ * fs_brick_range3d
+ *   Brick (bz, by, bx) holds the cells [8 b, 8 b + 8) of every axis, that is the nodes 8 b .. min(8 b + 8, N - 1);
+ *   nb_a = ceil((N_a - 1) / 8).  range: fp32 [K][nbz][nby][nbx][2], the minimum and maximum over the brick's finite
+ *   nodes (+inf, -inf when none); nonfinite: uint8 [K][nbz][nby][nbx], 1 when a node of the brick is NaN or +-inf.
+ *   With brick_range, brick_nonfinite (both as written here) and ws (fs_raycast3d_ws_bytes bytes) fs_raycast3d first
+ *   marks, in ws, the bricks no sample of which can contribute: none of its nodes is not finite and, for the range
+ *   [mn, mx] widened by 2^-20 max(|mn|, |mx|) (more than three nested fp32 interpolations can leave it by; not at all when
+ *   both are 0), in dvr A is 0
+ *   in every table row the range touches and one more at either end, in mip mx <= lo.  A ray that samples a cell of
+ *   such a brick jumps to the last sample it provably spends in the brick (faces pulled in by the margin above): it
+ *   lands early, never late.  Every sample jumped over would have added exactly 0 (e = 1, or c u = 0): the image is the
+ *   same bit for bit, only counts is smaller.
+ *   FS_ERR_NULLPTR: volumes, cameras, tf, spacing or image NULL, brick_range without brick_nonfinite and ws.
+ *   FS_ERR_SHAPE: K outside 1..65535, an extent below 2, more than 2^31 - 1 nodes, sstride below D*H*W, Hi or Wi outside
+ *   1..16*65535, n outside 2..FS_RC_MAX_TF.  FS_ERR_ARG: an unknown mode, lo >= hi or not finite, dt or a spacing not
+ *   finite and positive, t_min outside [0, 1), tf or image not 16-byte aligned, more than FS_RC_MAX_STEPS samples of dt
+ *   along the grown box (sum_a (N_a + 1) h_a / dt).  All of them are returned before anything is launched; the
+ *   _ws_bytes query launches nothing and returns the byte count or -(FS_ERR_*).
+ */
+enum { FS_RC_DVR = 0, FS_RC_MIP = 1 };
+#define FS_RC_BRICK 8
+#define FS_RC_MAX_TF 1024
+#define FS_RC_MAX_STEPS 4194304
+int fs_brick_range3d(const float* volumes, int K, int D, int H, int W, long long sstride, float* range,
+                     unsigned char* nonfinite, fs_stream_t stream);
+long long fs_raycast3d_ws_bytes(int K, int D, int H, int W);
+int fs_raycast3d(const float* volumes, int K, int D, int H, int W, long long sstride, const float* cameras,
+                 const float* tf, int n, double lo, double hi, double dt, const double* spacing, int mode, double t_min,
+                 int Hi, int Wi, const float* brick_range, const unsigned char* brick_nonfinite, unsigned char* ws,
+                 float* image, int* counts, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

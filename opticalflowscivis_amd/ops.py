@@ -3376,6 +3376,204 @@ def region_links(labels, flows, table):
 
 
 # --------------------------------------------------------------------------------------------
+# Ray casting: volumes to images through a transfer function (fs_raycast3d, fs_brick_range3d)
+# --------------------------------------------------------------------------------------------
+RC_MODES = {"dvr": 0, "mip": 1}  # FS_RC_DVR, FS_RC_MIP
+RC_BRICK = 8                     # FS_RC_BRICK: cells per brick and axis
+RC_MAX_TF = 1024                 # FS_RC_MAX_TF
+RC_MAX_STEPS = 4194304           # FS_RC_MAX_STEPS
+
+
+def _rc_volumes(volumes):
+    """(volumes, K, (D,H,W), nodes) of fp32 GPU volumes [K,D,H,W]; the step stride is kept where the kernel can use it."""
+    if not isinstance(volumes, torch.Tensor):
+        raise ValueError("volumes must be a tensor")
+    if not volumes.is_cuda:
+        raise ValueError("volumes must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (volumes.device,))
+    if volumes.dtype != torch.float32 or volumes.dim() != 4:
+        raise ValueError("volumes must be float32 [K,D,H,W], got %s %s" % (volumes.dtype, tuple(volumes.shape)))
+    K = int(volumes.shape[0])
+    sp = tuple(int(s) for s in volumes.shape[1:])
+    P = sp[0] * sp[1] * sp[2]
+    if K < 1 or K > 65535 or min(sp) < 2 or P > 2 ** 31 - 1:
+        raise ValueError("volumes must be 1..65535 volumes with every extent >= 2 and at most 2^31 - 1 nodes, got %s" %
+                         (tuple(volumes.shape),))
+    volumes = volumes.detach()
+    if not volumes[0].is_contiguous() or (K > 1 and volumes.stride(0) < P):
+        volumes = volumes.contiguous()
+    return volumes, K, sp, P
+
+
+def _rc_spacing(spacing):
+    try:
+        hs = [float(v) for v in spacing] if hasattr(spacing, "__len__") else [float(spacing)] * 3
+    except TypeError:
+        raise ValueError("spacing must be a number or three numbers, got %r" % (spacing,))
+    if len(hs) != 3 or not all(0 < h < float("inf") for h in hs):
+        raise ValueError("spacing must be one or 3 finite positive values (D,H,W), got %r" % (spacing,))
+    return hs
+
+
+def _rc_bricks(sp):
+    return tuple((s - 1 + RC_BRICK - 1) // RC_BRICK for s in sp)
+
+
+def _rc_image(image):
+    try:
+        Hi, Wi = (int(v) for v in image)
+    except (TypeError, ValueError):
+        raise ValueError("image must be (rows, columns), got %r" % (image,))
+    if not (1 <= Hi <= 16 * 65535 and 1 <= Wi <= 16 * 65535):
+        raise ValueError("image must be (rows, columns) within 1..%d, got %r" % (16 * 65535, image))
+    return Hi, Wi
+
+
+def raycast_cost(shape, image, K=1, dt=None, spacing=1.0, samples=None):
+    """(gathered bytes, flops) of one raycast call: every sample gathers the eight corners of its cell (32 bytes; most
+    come from lines a neighbouring ray or sample already fetched, so this is the gather traffic of the algorithm, not
+    HBM traffic) and costs about 60 flops (position, coverage, seven interpolations, the table, the exponential, the
+    blend); a pixel writes 16 bytes.  samples: the samples actually taken (the sum of `counts`); without it the upper
+    bound of one box diagonal of steps `dt` per pixel."""
+    sp = tuple(int(s) for s in shape)
+    if len(sp) != 3 or min(sp) < 2:
+        raise ValueError("shape must be (D,H,W) with every extent >= 2, got %r" % (shape,))
+    Hi, Wi = _rc_image(image)
+    hs = _rc_spacing(spacing)
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1, got %d" % K)
+    if samples is None:
+        step = 0.5 * min(hs) if dt is None else float(dt)
+        if not (0 < step < float("inf")):
+            raise ValueError("dt must be finite and positive, got %r" % (dt,))
+        diag = sum(((n + 1) * h) ** 2 for n, h in zip(sp, hs)) ** 0.5
+        samples = K * Hi * Wi * (int(diag / step) + 1)
+    samples = int(samples)
+    return 32 * samples + 16 * K * Hi * Wi, 60 * samples
+
+
+def brick_ranges(volumes):
+    """The value range of every brick of 8^3 cells (9^3 nodes) of K volumes, one launch (fs_brick_range3d).
+
+    volumes: fp32 [K,D,H,W] on a GPU, every extent >= 2.  Returns a dict on the device: range (fp32 [K,nbz,nby,nbx,2]: the
+    minimum and maximum over the brick's finite nodes; +inf, -inf when it has none) and nonfinite (uint8 [K,nbz,nby,nbx]:
+    1 when a node of the brick is NaN or +-inf), nb = ceil((N - 1) / 8) per axis.  ops.raycast takes the dict as `bricks`
+    and jumps over bricks that cannot contribute under its transfer function.  Never synchronises."""
+    volumes, K, sp, P = _rc_volumes(volumes)
+    nb = _rc_bricks(sp)
+    dev = volumes.device
+    res = {"range": torch.empty((K,) + nb + (2,), dtype=torch.float32, device=dev),
+           "nonfinite": torch.empty((K,) + nb, dtype=torch.uint8, device=dev)}
+    with torch.cuda.device(dev):
+        _call("fs_brick_range3d", volumes.data_ptr(), K, *sp, volumes.stride(0) if K > 1 else P, res["range"].data_ptr(),
+              res["nonfinite"].data_ptr(), _stream(volumes), algo_bytes=4 * K * P + 9 * K * nb[0] * nb[1] * nb[2])
+    return res
+
+
+def _rc_table(name, t, cols, dev):
+    """A small fp32 table given as a tensor, an array or nested lists -> (contiguous fp32 tensor on dev, its fp32 copy
+    in host memory or None when it already lived on a device)."""
+    host = not (isinstance(t, torch.Tensor) and t.is_cuda)
+    try:
+        t = t if isinstance(t, torch.Tensor) else torch.tensor(t)  # (a copy: an array may be read-only)
+    except Exception:
+        raise ValueError("%s must be a tensor or an array of numbers" % name)
+    if not t.dtype.is_floating_point and t.dtype not in (torch.int32, torch.int64):
+        raise ValueError("%s must hold numbers, got %s" % (name, t.dtype))
+    if t.dim() == 1 and cols == 18:
+        t = t[None]
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError("%s must be [n,%d], got %s" % (name, cols, tuple(t.shape)))
+    t = t.detach().to(torch.float32).contiguous()
+    return t.to(dev), t if host else None
+
+
+def raycast(volumes, cameras, tf, lo, hi, dt=None, spacing=1.0, mode="dvr", t_min=0.0, bricks=None, counts=False,
+            image=None):
+    """K volumes through K cameras and one transfer function to K RGBA images, one launch (fs_raycast3d).
+
+    volumes: fp32 [K,D,H,W] on a GPU; the step stride may be anything (stack[1::2] is read in place).  cameras: [K,18] (or
+    one camera [18] for all K), the 3-vectors o, ou, ov, d, du, dv in (x, y, z): pixel (i, j) -- column i of row j -- has the
+    origin o + i ou + j ov and the direction normalize(d + i du + j dv); render.orbit_camera makes them.  tf: [n,4] RGBA,
+    2 <= n <= RC_MAX_TF, spread uniformly over the values [lo, hi]; finite with A >= 0 (checked when it comes from the
+    host).  image: (rows, columns) of the pictures -- required.  spacing: the node spacing, one value or (D,H,W); node i of
+    an axis sits at i * spacing.  dt: the sample distance, half the smallest spacing by default.
+
+    A ray is sampled at (k + 1/2) dt from its origin, k = 0, 1, ...; a sample at index position q weighs
+    c = prod_a max(0, 1 - max(0, -q_a, q_a - (N_a - 1))) (1 inside, fading to 0 one cell outside), reads the trilinear value
+    v at q clamped to the box, and looks up the table at u = clamp((v - lo) / (hi - lo), 0, 1); a v that is not finite
+    contributes nothing.  mode "dvr": sigma = A c, e = exp(-sigma dt), C += T (1 - e) RGB, T *= e; the pixel is (C, 1 - T)
+    and the ray ends once T < t_min (0: never).  mode "mip": the pixel is the table's row at max_k c u.
+    include/flowsci_hip.h states the order of operations; tests/raycast_ref.py restates it.
+
+    bricks: ops.brick_ranges(volumes) -- rays jump over bricks in which the table's A is 0 (dvr) or nothing exceeds lo
+    (mip); the image is the same bit for bit.  counts: also return the samples every pixel gathered.
+
+    Returns a dict on the device: image (fp32 [K,Hi,Wi,4]) and, with counts, counts (int32 [K,Hi,Wi]).  Never
+    synchronises.  Nothing is differentiated."""
+    volumes, K, sp, P = _rc_volumes(volumes)
+    dev = volumes.device
+    if image is None:
+        raise ValueError("image=(rows, columns) is required")
+    Hi, Wi = _rc_image(image)
+    if mode not in RC_MODES:
+        raise ValueError("mode must be 'dvr' or 'mip', got %r" % (mode,))
+    hs = _rc_spacing(spacing)
+    try:
+        lo, hi, t_min = float(lo), float(hi), float(t_min)
+        dt = 0.5 * min(hs) if dt is None else float(dt)
+    except (TypeError, ValueError):
+        raise ValueError("lo, hi, dt and t_min must be numbers, got %r, %r, %r and %r" % (lo, hi, dt, t_min))
+    inf = float("inf")
+    if not (-inf < lo < hi < inf):
+        raise ValueError("the table spans lo < hi, both finite; got %r and %r" % (lo, hi))
+    if not (0 < dt < inf) or not (0 <= t_min < 1):
+        raise ValueError("dt must be finite and positive and t_min in [0, 1), got %r and %r" % (dt, t_min))
+    if sum((n + 1) * h for n, h in zip(sp, hs)) / dt > RC_MAX_STEPS:
+        raise ValueError("dt = %r takes more than %d samples through the volume" % (dt, RC_MAX_STEPS))
+    cams, _ = _rc_table("cameras", cameras, 18, dev)
+    if cams.shape[0] == 1 and K > 1:
+        cams = cams.expand(K, 18).contiguous()
+    if cams.shape[0] != K:
+        raise ValueError("cameras must be [%d,18] (or one camera), got %s" % (K, tuple(cams.shape)))
+    table, cpu = _rc_table("tf", tf, 4, dev)
+    if not 2 <= table.shape[0] <= RC_MAX_TF:
+        raise ValueError("the transfer function has 2..%d rows, got %d" % (RC_MAX_TF, table.shape[0]))
+    if cpu is not None:  # (a table that already lives on the device is not read back)
+        if not bool(torch.isfinite(cpu).all() and (cpu[:, 3] >= 0).all()):
+            raise ValueError("the transfer function must be finite with A >= 0")
+    if table.data_ptr() % 16:
+        table = table.clone()
+    nb = _rc_bricks(sp)
+    rng = flg = ws = None
+    if bricks is not None:
+        try:
+            rng, flg = bricks["range"], bricks["nonfinite"]
+        except (TypeError, KeyError, IndexError):
+            raise ValueError("bricks must be what ops.brick_ranges returned")
+        if (not isinstance(rng, torch.Tensor) or not isinstance(flg, torch.Tensor) or rng.device != dev or flg.device != dev
+                or rng.dtype != torch.float32 or flg.dtype != torch.uint8 or tuple(rng.shape) != (K,) + nb + (2,)
+                or tuple(flg.shape) != (K,) + nb):
+            raise ValueError("bricks must be ops.brick_ranges of these volumes: range fp32 %s and nonfinite uint8 %s on %s" %
+                             ((K,) + nb + (2,), (K,) + nb, dev))
+        rng, flg = rng.contiguous(), flg.contiguous()
+        n_ws = _lib.lib().fs_raycast3d_ws_bytes(K, *sp)
+        if n_ws < 0:
+            _lib.check(int(-n_ws), "fs_raycast3d_ws_bytes")
+        ws = torch.empty(n_ws, dtype=torch.uint8, device=dev)
+    res = {"image": torch.empty((K, Hi, Wi, 4), dtype=torch.float32, device=dev)}
+    if counts:
+        res["counts"] = torch.empty((K, Hi, Wi), dtype=torch.int32, device=dev)
+    nbytes, flops = raycast_cost(sp, (Hi, Wi), K, dt, hs)
+    with torch.cuda.device(dev):
+        _call("fs_raycast3d", volumes.data_ptr(), K, *sp, volumes.stride(0) if K > 1 else P, cams.data_ptr(),
+              table.data_ptr(), int(table.shape[0]), lo, hi, dt, (ctypes.c_double * 3)(*hs[::-1]), RC_MODES[mode], t_min,
+              Hi, Wi, _ptr(rng), _ptr(flg), _ptr(ws), res["image"].data_ptr(), _ptr(res.get("counts")), _stream(volumes),
+              algo_bytes=nbytes, algo_flops=flops)
+    return res
+
+
+# --------------------------------------------------------------------------------------------
 # Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
 # --------------------------------------------------------------------------------------------
 import numpy as _np

@@ -21,7 +21,8 @@ then needs the K - 1 (or more) step flows between the maps and measures no weigh
 one), 0 on background and on regions below --min-size; --track-ids the same shape with the track id (from 1) instead.
 
 Out of scope: edge-only (18) connectivity; periodic domains; components connected through time (4-D); vortex core lines;
-sub-node region boundaries; autograd; rendering; several series in one launch."""
+sub-node region boundaries; autograd; several series in one launch.  Pictures of the fields the regions were cut from:
+opticalflowscivis_amd/render.py (the `render` entry points)."""
 import argparse
 import json
 import math

@@ -19,8 +19,9 @@ of results.  A step's scale is 1 / (frames it spans * --dt); --spacing is the no
 
 Connected regions of the flag maps, their sizes and strengths, and their tracks through the series are
 opticalflowscivis_amd/regions.py (the `regions` entry points; --mask's file goes in there as it is).  Out of scope:
-swirling strength and the Delta criterion; eigenvectors; vortex core lines; a validity mask; autograd through the op;
-rendering."""
+swirling strength and the Delta criterion; eigenvectors; vortex core lines; a validity mask; autograd through the op.
+Pictures of --out: opticalflowscivis_amd/render.py (the `render` entry points take the file as --field, --plane picks the
+field)."""
 import argparse
 import json
 import os
