@@ -58,8 +58,9 @@ enum {
  *   430  fs_label_regions2d / fs_label_regions3d and their _ws_bytes queries, fs_region_stats2d / fs_region_stats3d,
  *        fs_region_follow2d / fs_region_follow3d (connected regions of flag maps, their table, where the flow carries them).
  *   440  fs_raycast3d / fs_raycast3d_ws_bytes, fs_brick_range3d (volumes to images: emission / absorption and maximum
- *        intensity through a transfer function, with per-brick value ranges to jump over empty space). */
-#define FS_ABI_VERSION 440
+ *        intensity through a transfer function, with per-brick value ranges to jump over empty space).
+ *   450  fs_iso_count3d / fs_iso_emit3d / fs_iso3d_ws_bytes (volumes to indexed triangle meshes: marching tetrahedra). */
+#define FS_ABI_VERSION 450
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -1055,6 +1056,64 @@ int fs_raycast3d(const float* volumes, int K, int D, int H, int W, long long sst
                  const float* tf, int n, double lo, double hi, double dt, const double* spacing, int mode, double t_min,
                  int Hi, int Wi, const float* brick_range, const unsigned char* brick_nonfinite, unsigned char* ws,
                  float* image, int* counts, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Isosurfaces -- K volumes and one isovalue to K indexed, watertight, consistently oriented triangle meshes: marching
+ * tetrahedra on the Kuhn split of every cell (no ambiguous cases; six corner lists and sixteen cases).
+ *   volumes: K fp32 volumes of D*H*W nodes, node (z, y, x) at (z * H + y) * W + x, volume k at + k * sstride elements
+ *     (>= D*H*W: every other volume of a stack is read in place); every extent >= 2.  Axis 0 runs along x (W), 1 along
+ *     y, 2 along z; spacing: HOST array of 3 doubles, the node spacing along x, y, z, each rounded to fp32 once.
+ *   iso is rounded to fp32 once.  A finite node is INSIDE iff f >= iso.
+ *   Edges.  Every node owns up to 7 edges, to the node at offset (dz, dy, dx) where that node exists:
+ *     e0 (0,0,1)  e1 (0,1,0)  e2 (1,0,0)  e3 (0,1,1)  e4 (1,0,1)  e5 (1,1,0)  e6 (1,1,1)
+ *     An edge is ACTIVE iff both ends are finite and exactly one end is inside.  An active edge carries one vertex.
+ *   Vertex position, in fp32 without fused multiply-adds, in exactly this order (a = the owner, b = the other end):
+ *     t = min(max((iso - fa) / (fb - fa), 0), 1);  per axis r  q_r = (float)i_r + (d_r ? t : 0);  p_r = q_r * (float)h_r
+ *     Vertices are stored as (x, y, z).  The vertices of a step are ordered by owner node index, then by edge number.
+ *   Tetrahedra.  A cell (z, y, x), every coordinate below extent - 1, is cut into 6 tetrahedra, one per permutation pi
+ *     of the axes (x = 0, y = 1, z = 2) in lexicographic order, with the corners c0 = the cell's origin node,
+ *     c1 = c0 + e_pi0, c2 = c1 + e_pi1, c3 = c0 + (1,1,1).  A cell with a corner that is not finite emits nothing.
+ *   Triangles of a tetrahedron; E(p,q) is the vertex on the edge between corners p and q (every such edge is one of
+ *     e0..e6 of the corner with the lower number):
+ *     0 or 4 corners inside: none.
+ *     1 or 3 inside: s the odd corner, a < b < c the others: (E(s,a), E(s,b), E(s,c)).
+ *     2 inside: i0 < i1 the inside corners, o0 < o1 the outside ones, q = (E(i0,o0), E(i0,o1), E(i1,o1), E(i1,o0)):
+ *       (q0, q1, q2) and (q0, q2, q3).
+ *     Orientation: the last two vertices of a triangle are swapped where needed so that, with every vertex moved to its
+ *     edge's midpoint in index space, (v1 - v0) x (v2 - v0) has a positive dot product with (centroid of the outside
+ *     corners - centroid of the inside corners): normals point towards lower values.  This depends on the case and the
+ *     tetrahedron only (csrc/iso_tables.hpp, derived by scripts/gen_iso_tables.py).
+ *   Faces are int32 vertex indices local to their step, ordered by cell index, then tetrahedron, then triangle.
+ *   Normals (optional).  Node gradient G: per axis (f(i+1) - f(i-1)) / (2 h), on the boundary (f(i+1) - f(i)) / h and
+ *     (f(i) - f(i-1)) / h.  G = Ga + t (Gb - Ga);  n = -G / |G|, or (0,0,0) where |G| is 0 or not finite.
+ *   Values (optional).  F <= FS_ISO_MAX_VALUES planes of a second field, fp32 [K][F][D*H*W]:  w = wa + t (wb - wa).
+ *     Fused multiply-adds are allowed in normals and values.
+ *   The result is bitwise reproducible: no atomic decides a position or an order.
+ *
+ * fs_iso_count3d -- one launch.  ws: fs_iso3d_ws_bytes bytes, 4-byte aligned, written as
+ *     int32 nv[K*D*H], int32 nt[K*D*H]: per row (k, z, y) the vertices its nodes own and the triangles its cells emit;
+ *     padding to a multiple of 16 bytes;  uint8 mask[K][D*H*W]: bit e of a node's byte = its edge e is active.
+ * The caller turns nv and nt into row_offsets, int64 [2][K*D*H + 1] in DEVICE memory: the exclusive prefix sums of nv,
+ *   then of nt, over all rows, each with the total at the end.  V and T are those totals.  (Step k's vertices are
+ *   row_offsets[0][k*D*H] .. row_offsets[0][(k+1)*D*H].)
+ * fs_iso_emit3d -- one launch (none when V and T are 0).  It recomputes every row's in-row prefix from the masks; a
+ *   vertex is row (row offset of the owner's row + in-row prefix at the owner + rank of the edge within the owner's
+ *   mask) of vertices [V][3], normals [V][3] (NULL: not wanted) and values_out [V][F]; faces is int32 [T][3].  Nothing is
+ *   written at or beyond row V or T.  status: int32 [1], zeroed by the CALLER; bit 0 is set when the masks and the
+ *   offsets disagree (a row's counts, an index outside its step) -- the outputs are then not a mesh.
+ *   FS_ERR_NULLPTR: volumes, spacing, ws, row_offsets or status NULL; vertices with V > 0, faces with T > 0, values with
+ *   F > 0, values_out with F > 0 and V > 0.  FS_ERR_SHAPE: K < 1 or K*D*H above 2^31 - 1, an extent below 2, more than
+ *   2^31 - 1 nodes, sstride below D*H*W, F outside 0..FS_ISO_MAX_VALUES.  FS_ERR_ARG: iso not finite (as fp32), a spacing
+ *   not finite and positive (as fp32), V or T negative, ws not 4-byte aligned.  All of them are returned before anything is
+ *   launched; the _ws_bytes query launches nothing and returns the byte count or -(FS_ERR_*).
+ */
+#define FS_ISO_MAX_VALUES 8
+long long fs_iso3d_ws_bytes(int K, int D, int H, int W);
+int fs_iso_count3d(const float* volumes, int K, int D, int H, int W, long long sstride, double iso, unsigned char* ws,
+                   fs_stream_t stream);
+int fs_iso_emit3d(const float* volumes, int K, int D, int H, int W, long long sstride, double iso, const double* spacing,
+                  const unsigned char* ws, const long long* row_offsets, long long V, long long T, const float* values,
+                  int F, float* vertices, float* normals, float* values_out, int* faces, int* status, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

@@ -1,0 +1,200 @@
+"""Geometry out of what the pipeline writes: every frame of a series of volumes (`reconstruct`'s frames, or a field of
+`ftle`, `vortex` or `regions`) becomes one indexed triangle mesh of the surface f = iso, extracted on the device by
+marching tetrahedra (ops.isosurface: a classify-and-count launch and a gather-and-emit launch per `--chunk` of frames),
+and is written as a binary PLY (ParaView, Blender, MeshLab) or an .npz.  The flow3d `isosurface` entry point:
+
+    python -m opticalflowscivis_amd.flow3d.isosurface --field vg.npy --plane 4 --iso -0.02 --color-field vg.npy \\
+        --color-plane 3 --spacing 1 1 1 --mesh-dir meshes --format ply --json r.json
+    python -m opticalflowscivis_amd.flow3d.isosurface --seq frames.npy --iso 0.5 --mesh-dir meshes --format npz
+
+--field takes [K, D,H,W] or [K, NP, D,H,W] (--plane picks one of the NP planes), as flow3d.render does.  --color-field
+names a second field of the same steps and extent ([K, D,H,W] or [K, NP, D,H,W] with --color-plane) whose values are
+interpolated to the vertices and written as the per-vertex property `value0`.  --spacing is one value or D H W.  A mesh
+has vertices (x, y, z), unit normals pointing towards lower values, the optional values and int32 faces; it is watertight
+and consistently oriented wherever the surface does not leave the volume or meet nodes that are not finite.  --mesh-dir
+gets frame_%04d.ply (binary little-endian: x y z nx ny nz [value0 ...], then vertex_indices) or frame_%04d.npz (vertices,
+normals, values, faces).  The JSON holds per frame its time (index * --dt), vertices, faces, area, the signed enclosed
+volume (positive where the surface encloses higher values), boundary_edges (edges not shared by exactly two faces: 0 for
+a closed surface) and status.
+
+Each chunk of frames is uploaded once, extracted by two launches, downloaded and dropped: device memory is one chunk of
+volumes, one byte per node of workspace, and the chunk's meshes.
+
+Out of scope: 2-D contour lines; marching cubes tables; skipping empty bricks through ops.brick_ranges (a natural
+follow-up: a brick whose range misses iso owns nothing); mesh simplification and smoothing; restricting the surface to
+labelled regions; autograd; several isovalues per launch."""
+import argparse
+import json
+import os
+import struct
+import time
+
+import numpy as np
+import torch
+
+from . import ops
+from .render import _source
+
+
+def mesh_stats(vertices, faces):
+    """Of one indexed triangle mesh (vertices [V,3], faces [T,3]; tensors on any device, or arrays), in fp64 (plumbing:
+    torch): area, volume -- the signed enclosed volume sum v0 . (v1 x v2) / 6, meaningful for a closed surface, positive
+    when the normals point outwards -- bbox ([2,3]: minimum and maximum of the vertices, None without any) and
+    boundary_edges, the undirected edges that are not shared by exactly two faces."""
+    v = torch.as_tensor(vertices).to(torch.float64).reshape(-1, 3)
+    f = torch.as_tensor(faces).to(v.device).to(torch.int64).reshape(-1, 3)
+    if f.shape[0] == 0:
+        return {"area": 0.0, "volume": 0.0, "bbox": [v.min(0).values.tolist(), v.max(0).values.tolist()] if len(v) else None,
+                "boundary_edges": 0}
+    v0, v1, v2 = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    area = 0.5 * torch.linalg.cross(v1 - v0, v2 - v0).norm(dim=1).sum()
+    vol = (v0 * torch.linalg.cross(v1, v2)).sum() / 6.0
+    a = torch.cat([f[:, 0], f[:, 1], f[:, 2]])
+    b = torch.cat([f[:, 1], f[:, 2], f[:, 0]])
+    key = torch.minimum(a, b) * max(int(v.shape[0]), 1) + torch.maximum(a, b)
+    _, counts = torch.unique(key, return_counts=True)
+    return {"area": float(area), "volume": float(vol), "bbox": [v.min(0).values.tolist(), v.max(0).values.tolist()],
+            "boundary_edges": int((counts != 2).sum())}
+
+
+def write_ply(path, vertices, normals, faces, values=None):
+    """A binary little-endian PLY (struct only): per vertex x y z nx ny nz and one float property value<i> per column of
+    `values`, per face a uchar count of 3 and three int32 vertex_indices."""
+    v = np.ascontiguousarray(vertices, dtype="<f4").reshape(-1, 3)
+    n = np.ascontiguousarray(normals, dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype="<i4").reshape(-1, 3)
+    w = np.zeros((v.shape[0], 0), "<f4") if values is None else np.ascontiguousarray(values, dtype="<f4").reshape(v.shape[0], -1)
+    if n.shape != v.shape:
+        raise ValueError("normals must match vertices, got %s and %s" % (n.shape, v.shape))
+    head = ["ply", "format binary_little_endian 1.0", "comment opticalflowscivis_amd isosurface",
+            "element vertex %d" % v.shape[0]]
+    head += ["property float %s" % p for p in ("x", "y", "z", "nx", "ny", "nz")]
+    head += ["property float value%d" % i for i in range(w.shape[1])]
+    head += ["element face %d" % f.shape[0], "property list uchar int vertex_indices", "end_header"]
+    cols = 6 + w.shape[1]
+    with open(path, "wb") as out:
+        out.write(("\n".join(head) + "\n").encode("ascii"))
+        rows = np.concatenate([v, n, w], axis=1)
+        for i in range(0, rows.shape[0], 16384):  # (blocks: struct takes its numbers as arguments)
+            part = rows[i:i + 16384]
+            out.write(struct.pack("<%df" % (part.shape[0] * cols), *part.reshape(-1).tolist()))
+        rec = struct.Struct("<Biii")
+        for i in range(0, f.shape[0], 16384):
+            out.write(b"".join(rec.pack(3, *t) for t in f[i:i + 16384].tolist()))
+
+
+def isosurface_series(volumes_of, n_frames, iso, spacing=1.0, values_of=None, chunk=4, times=None, sink=None):
+    """Meshes of the n_frames volumes that volumes_of(j0, j1) -> fp32 [j1 - j0, D, H, W] on the device hands out `chunk`
+    at a time (each exactly once; one ops.isosurface call -- two launches -- per chunk).  values_of(j0, j1) -> fp32
+    [j1 - j0, F, D, H, W] or None.  times: the time of every frame (default its index).  sink(j, mesh): called with every
+    frame's mesh, a dict of host arrays vertices, normals, faces and values (None without values_of).
+
+    Returns a dict: frames (one dict per frame: frame, time, vertices, faces, area, volume, bbox, boundary_edges, status)
+    and the totals time_load_s, time_kernel_s.  FlowsciKernelError when a chunk's status is set."""
+    chunk = max(1, int(chunk))
+    n_frames = int(n_frames)
+    times = list(range(n_frames)) if times is None else [float(t) for t in times]
+    if len(times) != n_frames:
+        raise ValueError("times must name the %d frames, got %d" % (n_frames, len(times)))
+    rows = []
+    t_load = t_kernel = 0.0
+    for j0 in range(0, n_frames, chunk):
+        j1 = min(n_frames, j0 + chunk)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        v = volumes_of(j0, j1)
+        w = values_of(j0, j1) if values_of is not None else None
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        r = ops.isosurface(v, iso, spacing, True, w)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        t_load += t1 - t0
+        t_kernel += t2 - t1
+        status = int(r["status"].cpu()[0])
+        ops.isosurface_check({"status": status})
+        vo, fo = r["vertex_offsets"].cpu().tolist(), r["face_offsets"].cpu().tolist()
+        for j in range(j0, j1):
+            k = j - j0
+            vert, faces = r["vertices"][vo[k]:vo[k + 1]], r["faces"][fo[k]:fo[k + 1]]
+            st = mesh_stats(vert, faces)
+            rows.append(dict({"frame": j, "time": times[j], "vertices": vo[k + 1] - vo[k], "faces": fo[k + 1] - fo[k]}, **st,
+                             status=status))
+            if sink is not None:
+                sink(j, {"vertices": vert.cpu().numpy(), "normals": r["normals"][vo[k]:vo[k + 1]].cpu().numpy(),
+                         "faces": faces.cpu().numpy(),
+                         "values": r["values"][vo[k]:vo[k + 1]].cpu().numpy() if w is not None else None})
+        del v, w, r
+    return {"frames": rows, "time_load_s": t_load, "time_kernel_s": t_kernel}
+
+
+def _args():
+    ap = argparse.ArgumentParser(description="Extract the isosurface of every frame of a series of volumes or 3-D fields")
+    ap.add_argument("--seq", help=".npy sequence [T,D,H,W]")
+    ap.add_argument("--field", help=".npy field [K,D,H,W] or [K,NP,D,H,W] as ftle, vortex and regions write them")
+    ap.add_argument("--plane", type=int, default=0, help="the plane of a [K,NP,D,H,W] --field")
+    ap.add_argument("--iso", type=float, required=True, help="the isovalue: a node is inside where f >= iso")
+    ap.add_argument("--color-field", default=None, metavar="FIELD.npy",
+                    help="a second field [K,D,H,W] or [K,NP,D,H,W] sampled at the vertices")
+    ap.add_argument("--color-plane", type=int, default=0, help="the plane of a [K,NP,D,H,W] --color-field")
+    ap.add_argument("--spacing", type=float, nargs="+", default=[1.0], help="node spacing: one value or D H W")
+    ap.add_argument("--chunk", type=int, default=4, help="frames uploaded at a time and handed to one pair of launches")
+    ap.add_argument("--mesh-dir", default=None, metavar="DIR", help="write frame_%%04d.<format> here")
+    ap.add_argument("--format", choices=("ply", "npz"), default="ply")
+    ap.add_argument("--dt", type=float, default=1.0, help="the time one frame spans: a frame's time is its index * dt")
+    ap.add_argument("--json", default=None, help="write the report as JSON here")
+    return ap
+
+
+def main3d(argv=None):
+    """flow3d: one mesh per frame of a series of volumes."""
+    args = _args().parse_args(argv)
+    if args.chunk < 1:
+        raise SystemExit("--chunk must be >= 1")
+    if len(args.spacing) not in (1, 3) or not all(0 < h < float("inf") for h in args.spacing):
+        raise SystemExit("--spacing takes one or 3 finite positive values")
+    if not -float("inf") < args.iso < float("inf"):
+        raise SystemExit("--iso must be finite")
+    a, take, name = _source(args, 3)
+    K = int(a.shape[0])
+    sp = tuple(int(s) for s in take(0, 1).shape[1:])
+    spacing = args.spacing[0] if len(args.spacing) == 1 else tuple(args.spacing)
+    dev = torch.device("cuda")
+    source = lambda j0, j1: torch.from_numpy(np.array(take(j0, j1), np.float32)).to(dev)
+    colors = None
+    if args.color_field:
+        c = np.load(args.color_field, mmap_mode="r")
+        if c.ndim == 5 and not 0 <= args.color_plane < c.shape[1]:
+            raise SystemExit("--color-plane must lie in 0..%d" % (c.shape[1] - 1))
+        if c.ndim not in (4, 5) or c.shape[0] < K or tuple(c.shape[-3:]) != sp:
+            raise SystemExit("--color-field must be [>= %d, %s] or [K,NP,...], got %s" % (K, sp, c.shape))
+        pick = (lambda j0, j1: c[j0:j1, args.color_plane]) if c.ndim == 5 else (lambda j0, j1: c[j0:j1])
+        colors = lambda j0, j1: torch.from_numpy(np.array(pick(j0, j1), np.float32)[:, None]).to(dev)
+    if args.mesh_dir:
+        os.makedirs(args.mesh_dir, exist_ok=True)
+
+    def sink(j, m):
+        if not args.mesh_dir:
+            return
+        path = os.path.join(args.mesh_dir, "frame_%04d.%s" % (j, args.format))
+        if args.format == "ply":
+            write_ply(path, m["vertices"], m["normals"], m["faces"], m["values"])
+        else:
+            np.savez(path, vertices=m["vertices"], normals=m["normals"], faces=m["faces"],
+                     values=m["values"] if m["values"] is not None else np.zeros((len(m["vertices"]), 0), np.float32))
+
+    res = isosurface_series(source, K, args.iso, spacing, colors, args.chunk, [j * args.dt for j in range(K)], sink)
+    doc = {"source": name, "shape": list(sp), "plane": args.plane if args.field and a.ndim == 5 else None, "iso": args.iso,
+           "color_field": os.path.basename(args.color_field) if args.color_field else None,
+           "color_plane": args.color_plane if args.color_field else None, "spacing": list(args.spacing),
+           "format": args.format, "frames": res["frames"], "time_load_s": res["time_load_s"],
+           "time_kernel_s": res["time_kernel_s"]}
+    for w in res["frames"]:
+        print("%s frame %d t %.4g: %d vertices  %d faces  area %.6g  volume %.6g  boundary edges %d" % (
+            name, w["frame"], w["time"], w["vertices"], w["faces"], w["area"], w["volume"], w["boundary_edges"]))
+    print("load %.3f s  kernel %.4f s" % (res["time_load_s"], res["time_kernel_s"]))
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            json.dump(doc, f, indent=1)
+    return doc

@@ -3574,6 +3574,134 @@ def raycast(volumes, cameras, tf, lo, hi, dt=None, spacing=1.0, mode="dvr", t_mi
 
 
 # --------------------------------------------------------------------------------------------
+# Isosurfaces: volumes to indexed triangle meshes by marching tetrahedra (fs_iso_count3d, fs_iso_emit3d)
+# --------------------------------------------------------------------------------------------
+ISO_MAX_VALUES = 8  # FS_ISO_MAX_VALUES
+
+
+def isosurface_cost(shape, K=1, V=0, T=0, F=0, normals=True, op="count"):
+    """(HBM bytes, flops) the algorithm needs for one pass of ops.isosurface over K volumes of spatial `shape`.  "count":
+    every node read once (4 bytes), its mask byte written, two int32 per row.  "emit": the mask bytes read, the V vertices
+    (12 bytes, 12 more with normals, 4 F with values) and the T faces (12 bytes) written; the nodes, gradients and value
+    planes gathered around cut cells are on top and depend on the surface.  The work is integer work: flops 0."""
+    sp = tuple(int(s) for s in shape)
+    if len(sp) != 3 or min(sp) < 2:
+        raise ValueError("shape must be (D,H,W) with every extent >= 2, got %r" % (shape,))
+    K, V, T, F = int(K), int(V), int(T), int(F)
+    if K < 1 or V < 0 or T < 0 or not 0 <= F <= ISO_MAX_VALUES:
+        raise ValueError("K >= 1, V, T >= 0 and F in 0..%d, got %d, %d, %d, %d" % (ISO_MAX_VALUES, K, V, T, F))
+    P = sp[0] * sp[1] * sp[2]
+    if op == "count":
+        return K * (5 * P + 8 * sp[0] * sp[1]), 0
+    if op == "emit":
+        return K * P + V * (12 + (12 if normals else 0) + 4 * F) + 12 * T, 0
+    raise ValueError("op must be 'count' or 'emit', got %r" % (op,))
+
+
+def isosurface_count(volumes, iso):
+    """The first pass of ops.isosurface on its own (fs_iso_count3d): the workspace (uint8, the per-row counts and the
+    per-node masks of active edges) and row_offsets, int64 [2, K*D*H + 1] on the device: the exclusive prefix sums of the
+    rows' vertex and triangle counts (plumbing: torch.cumsum).  Never synchronises."""
+    volumes, K, sp, P = _rc_volumes(volumes)
+    try:
+        iso = float(iso)
+    except (TypeError, ValueError):
+        raise ValueError("iso must be a number, got %r" % (iso,))
+    if not -float("inf") < iso < float("inf"):
+        raise ValueError("iso must be finite, got %r" % (iso,))
+    dev = volumes.device
+    R = K * sp[0] * sp[1]
+    nb = _lib.lib().fs_iso3d_ws_bytes(K, *sp)
+    if nb < 0:
+        _lib.check(int(-nb), "fs_iso3d_ws_bytes")
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    nbytes, flops = isosurface_cost(sp, K, op="count")
+    with torch.cuda.device(dev):
+        _call("fs_iso_count3d", volumes.data_ptr(), K, *sp, volumes.stride(0) if K > 1 else P, iso, ws.data_ptr(),
+              _stream(volumes), algo_bytes=nbytes, algo_flops=flops)
+    off = torch.zeros((2, R + 1), dtype=torch.int64, device=dev)
+    off[:, 1:] = torch.cumsum(ws[:8 * R].view(torch.int32).view(2, R), 1, dtype=torch.int64)
+    return ws, off
+
+
+def isosurface_emit(volumes, iso, spacing, ws, row_offsets, V, T, normals=True, values=None):
+    """The second pass of ops.isosurface on its own (fs_iso_emit3d), on what isosurface_count returned and the totals V
+    and T as host ints.  Returns (vertices, normals or None, values or None, faces, status) on the device.  Never
+    synchronises."""
+    volumes, K, sp, P = _rc_volumes(volumes)
+    hs = _rc_spacing(spacing)
+    dev = volumes.device
+    V, T = int(V), int(T)
+    F = 0 if values is None else int(values.shape[1])
+    vert = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    nrm = torch.empty((V, 3), dtype=torch.float32, device=dev) if normals else None
+    vout = torch.empty((V, F), dtype=torch.float32, device=dev) if F else None
+    faces = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if V or T:
+        nbytes, flops = isosurface_cost(sp, K, V, T, F, normals, op="emit")
+        with torch.cuda.device(dev):
+            _call("fs_iso_emit3d", volumes.data_ptr(), K, *sp, volumes.stride(0) if K > 1 else P, float(iso),
+                  (ctypes.c_double * 3)(*hs[::-1]), ws.data_ptr(), row_offsets.data_ptr(), V, T, _ptr(values), F,
+                  vert.data_ptr(), _ptr(nrm), _ptr(vout), faces.data_ptr(), status.data_ptr(), _stream(volumes),
+                  algo_bytes=nbytes, algo_flops=flops)
+    return vert, nrm, vout, faces, status
+
+
+def isosurface(volumes, iso, spacing=1.0, normals=True, values=None):
+    """K volumes and one isovalue to K indexed triangle meshes, two launches (fs_iso_count3d, fs_iso_emit3d): marching
+    tetrahedra on the Kuhn split of every cell -- watertight and consistently oriented by construction.
+
+    volumes: fp32 [K,D,H,W] on a GPU, every extent >= 2; the step stride may be anything (stack[::2] is read in place).
+    A finite node is inside iff f >= fp32(iso); a cell with a corner that is not finite emits nothing.  spacing: the node
+    spacing, one value or (D,H,W); node i of an axis sits at i * spacing.  values: optional fp32 [K,F,D,H,W] on the same
+    device, F <= 8, interpolated to the vertices.  include/flowsci_hip.h states the definition; tests/isosurface_ref.py
+    restates it.
+
+    The numbers of vertices and faces depend on the data, so this SYNCHRONISES: exactly once, between the two launches, to
+    learn the steps' offsets (the prefix sum over the rows' counts is torch's).  `status` is therefore returned, not read:
+    ops.isosurface_check(result) reads it and raises FlowsciKernelError when it is set (isosurface.isosurface_series does
+    so with the download it makes anyway).  ValueError when a step has 2^31 - 1 or more vertices or faces.
+
+    Returns a dict on the device: vertices (fp32 [V,3], (x, y, z), a step's in the order of owner node, then edge), normals
+    (fp32 [V,3], unit, towards lower values, from the interpolated central-difference gradient; only with normals), values
+    (fp32 [V,F]; only with values), faces (int32 [T,3], indices local to their step, by cell, tetrahedron, triangle),
+    vertex_offsets and face_offsets (int64 [K+1]: step k owns rows offsets[k] .. offsets[k+1]) and status (int32 [1]).
+    Bitwise reproducible.  Nothing is differentiated."""
+    volumes, K, sp, P = _rc_volumes(volumes)
+    dev = volumes.device
+    _rc_spacing(spacing)
+    if values is not None:
+        values = _need_cuda_f32("values", values, 5)
+        F = int(values.shape[1])
+        if tuple(values.shape) != (K, F) + sp or not 1 <= F <= ISO_MAX_VALUES or values.device != dev:
+            raise ValueError("values must be [K,F,D,H,W] = [%d, 1..%d, %s] on %s, got %s on %s" %
+                             (K, ISO_MAX_VALUES, sp, dev, tuple(values.shape), values.device))
+    ws, off = isosurface_count(volumes, iso)
+    steps = off[:, ::sp[0] * sp[1]].contiguous()  # [2, K+1]
+    host = steps.cpu().numpy()  # the one synchronisation
+    per_step = _np.diff(host, axis=1)
+    if per_step.size and int(per_step.max()) >= 2 ** 31 - 1:
+        raise ValueError("a step has %d vertices or faces: the limit is 2^31 - 2" % int(per_step.max()))
+    V, T = int(host[0, -1]), int(host[1, -1])
+    vert, nrm, vout, faces, status = isosurface_emit(volumes, iso, spacing, ws, off, V, T, normals, values)
+    res = {"vertices": vert, "faces": faces, "vertex_offsets": steps[0], "face_offsets": steps[1], "status": status}
+    if normals:
+        res["normals"] = nrm
+    if values is not None:
+        res["values"] = vout
+    return res
+
+
+def isosurface_check(result):
+    """Raises FlowsciKernelError when ops.isosurface's `status` is set (the masks and offsets of its two passes
+    disagreed: the arrays are then not a mesh).  Synchronises."""
+    st = int(result["status"].view(-1)[0]) if isinstance(result["status"], torch.Tensor) else int(result["status"])
+    if st != 0:
+        raise _lib.FlowsciKernelError("fs_iso_emit3d: the masks and the row offsets disagree (status %d)" % st)
+
+
+# --------------------------------------------------------------------------------------------
 # Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
 # --------------------------------------------------------------------------------------------
 import numpy as _np

@@ -22,8 +22,9 @@ Each chunk of frames is uploaded once, rendered by one launch (plus one for the 
 empty space; --no-bricks leaves it out -- the pictures are the same bit for bit) and dropped: device memory is one chunk
 of volumes and of images.
 
-Out of scope: gradient shading; isosurface extraction; depth output; label and categorical volumes; several fields in one
-picture; autograd; an interactive viewer."""
+Out of scope: gradient shading; depth output; label and categorical volumes; several fields in one picture; autograd; an
+interactive viewer.  Isosurface extraction -- the geometry behind an `iso:<value>` picture, as triangle meshes -- is
+opticalflowscivis_amd/isosurface.py (`flow3d.isosurface`)."""
 import argparse
 import json
 import math
