@@ -18,6 +18,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .error import select_from_psnr
+from .rife import load_pretrained
 
 
 def _pad32(x, nd):
@@ -222,12 +223,7 @@ def main(Model, nd, argv=None):
     ap.add_argument("--out", default=None, help="write the results as JSON here")
     args = ap.parse_args(argv)
     dev = torch.device("cuda")
-    model = Model(-1, device=dev)
-    try:
-        model.load_model("flownet.pkl", args.model)
-    except FileNotFoundError:
-        print("no flownet.pkl under %s: using random-init weights" % args.model)
-    model.eval()
+    model = load_pretrained(Model, args.model, dev)
     if args.seq:
         seq = _load_seq(args.seq, nd, args.normalize)
         name = os.path.basename(args.seq)

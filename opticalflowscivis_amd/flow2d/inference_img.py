@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from ..evaluate import ratio_inference
+from ..rife import load_pretrained
 from .model.RIFE import Model
 
 ND = 2
@@ -29,12 +30,7 @@ def main():
     ap.add_argument('--rmaxcycles', default=8, type=int, help='limit of bisection cycles')
     args = ap.parse_args()
     dev = torch.device('cuda')
-    model = Model(-1, device=dev)
-    try:
-        model.load_model('flownet.pkl', args.model)
-    except FileNotFoundError:
-        print('no flownet.pkl under %s: using random-init weights' % args.model)
-    model.eval()
+    model = load_pretrained(Model, args.model, dev)
     a, b = (torch.from_numpy(np.load(p).astype(np.float32)).to(dev) for p in args.img)
     a, b = a.reshape((1, 1) + a.shape[-ND:]), b.reshape((1, 1) + b.shape[-ND:])
     sp = a.shape[2:]

@@ -43,6 +43,7 @@ import torch
 
 from . import ops
 from .evaluate import _pad32
+from .rife import load_pretrained
 
 STATS = ("epe", "epe_noc", "epe_occ", "rmse", "ae_deg", "fl", "fl_noc", "fl_occ", "max_epe", "n_valid", "n_noc",
          "n_nonfinite")
@@ -310,12 +311,7 @@ def main_rife(Model, nd, argv=None):
     """flow2d / flow3d: the final IFNet flow at the mid frame of (t, t+gap)."""
     args = check_args(_common_args(nd, "score the flows of a RIFE model against known motion").parse_args(argv))
     dev = torch.device("cuda")
-    model = Model(-1, device=dev)
-    try:
-        model.load_model("flownet.pkl", args.model)
-    except FileNotFoundError:
-        print("no flownet.pkl under %s: using random-init weights" % args.model)
-    model.eval()
+    model = load_pretrained(Model, args.model, dev)
     frames, gt, name = _sequence(args, nd, dev)
     pairs = rife_pairs(frames.shape[0], args.gap)
     targets = []

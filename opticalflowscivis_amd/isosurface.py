@@ -24,7 +24,6 @@ Out of scope: 2-D contour lines; marching cubes tables; skipping empty bricks th
 follow-up: a brick whose range misses iso owns nothing); mesh simplification and smoothing; restricting the surface to
 labelled regions; autograd; several isovalues per launch."""
 import argparse
-import json
 import os
 import struct
 import time
@@ -33,7 +32,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .render import _source
+from .render import series_source
+from .stepflows import write_report
 
 
 def mesh_stats(vertices, faces):
@@ -155,7 +155,7 @@ def main3d(argv=None):
         raise SystemExit("--spacing takes one or 3 finite positive values")
     if not -float("inf") < args.iso < float("inf"):
         raise SystemExit("--iso must be finite")
-    a, take, name = _source(args, 3)
+    a, take, name = series_source(args, 3)
     K = int(a.shape[0])
     sp = tuple(int(s) for s in take(0, 1).shape[1:])
     spacing = args.spacing[0] if len(args.spacing) == 1 else tuple(args.spacing)
@@ -193,8 +193,5 @@ def main3d(argv=None):
         print("%s frame %d t %.4g: %d vertices  %d faces  area %.6g  volume %.6g  boundary edges %d" % (
             name, w["frame"], w["time"], w["vertices"], w["faces"], w["area"], w["volume"], w["boundary_edges"]))
     print("load %.3f s  kernel %.4f s" % (res["time_load_s"], res["time_kernel_s"]))
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        with open(args.json, "w") as f:
-            json.dump(doc, f, indent=1)
+    write_report(doc, args.json)
     return doc

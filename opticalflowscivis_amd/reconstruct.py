@@ -34,6 +34,7 @@ import torch
 from . import ops
 from .data.series import STORED_DTYPES, SeriesWriter, encode_numpy, load_series, series_layout
 from .evaluate import _pad32, bisect_keyframes, bisection_groups
+from .rife import load_pretrained
 
 NORMALIZE = ("global", "none")
 STAT_NAMES = ("min", "max", "n_low", "n_high", "n_nonfinite")
@@ -364,12 +365,7 @@ def main(Model, nd, argv=None):
         if path and os.path.exists(path) and not args.overwrite:
             raise FileExistsError("%s exists: pass --overwrite to replace it" % path)
     dev = torch.device("cuda")
-    model = Model(-1, device=dev)
-    try:
-        model.load_model("flownet.pkl", args.model)
-    except FileNotFoundError:
-        print("no flownet.pkl under %s: using random-init weights" % args.model)
-    model.eval()
+    model = load_pretrained(Model, args.model, dev)
     extra = tuple(stored.shape[1:stored.ndim - nd])
     writer = SeriesWriter(args.out, (T_out,) + extra + sp, out_dt, args.overwrite, source=args.series)
     flow_writer = None

@@ -10,7 +10,7 @@ entry points:
     python -m opticalflowscivis_amd.flow2d.regions --flows flows.npy --mask m.npy --require 1 --reject 128 --json r.json
     python -m opticalflowscivis_amd.upflow.regions --dataset rectangle2d --json r.json
 
-The step flows are those of `vortex` and `trace` (trace.step_chain over the flows flow_eval extracts, or --flows).  Step
+The step flows are those of `vortex` and `trace` (stepflows.step_chain over the flows flow_eval extracts, or --flows).  Step
 flow j gives label map j: it lives on the grid of the frame the step starts at, and the same flow carries map j onto
 map j + 1, so K step flows give K maps and K - 1 sets of links.  Each chunk of step flows is estimated once; the last
 label map of a chunk stays on the device and is linked to the first of the next, so nothing but timing depends on
@@ -24,15 +24,13 @@ Out of scope: edge-only (18) connectivity; periodic domains; components connecte
 sub-node region boundaries; autograd; several series in one launch.  Pictures of the fields the regions were cut from:
 opticalflowscivis_amd/render.py (the `render` entry points)."""
 import argparse
-import json
 import math
-import os
 import time
 
 import numpy as np
 import torch
 
-from . import flow_eval, ops, trace, vortex
+from . import ops, stepflows
 
 CRITERIA = {"q": (("q",), ops.VG_FLAG_Q), "l2": (("l2",), ops.VG_FLAG_L2),
             "both": (("q", "l2"), ops.VG_FLAG_Q | ops.VG_FLAG_L2), "mask": ((), None)}
@@ -166,7 +164,7 @@ def regions_series(step_flows, n_steps, sp, criterion="q", connectivity="face", 
         frames = list(range(n_steps + 1)) if frames is None else list(frames)
         if len(frames) != n_steps + 1:
             raise ValueError("frames must name the %d frames the chain visits, got %d" % (n_steps + 1, len(frames)))
-        scales = vortex.step_scales(frames, dt)
+        scales = stepflows.step_scales(frames, dt)
         require, reject = CRITERIA[criterion][1], ops.VG_FLAG_NONFINITE
         fields = [n for n in ops.VG_FIELDS if n in CRITERIA[criterion][0] or n in names]
     cols, links, rows = [], [], []
@@ -243,23 +241,9 @@ def regions_series(step_flows, n_steps, sp, criterion="q", connectivity="face", 
 def _args(nd, desc, model):
     sp = ",".join("DHW"[3 - nd:])
     ap = argparse.ArgumentParser(description=desc)
-    ap.add_argument("--dataset", choices=flow_eval.DATASETS[nd], help="synthetic sequence with known motion")
-    ap.add_argument("--seq", help=".npy sequence [T,%s] in [0,1]" % sp)
-    ap.add_argument("--flows", metavar="PATH", help="skip the model: a [K,%d,%s] .npy of consecutive step flows, or a "
-                    "directory of flow_%%03d_to_%%03d.npy files chained from --start" % (nd, sp))
-    ap.add_argument("--start", type=int, default=0, help="first frame of a --flows chain")
-    ap.add_argument("--frames", type=int, default=9, help="frames of a synthetic sequence")
-    ap.add_argument("--size", type=int, nargs="+", default=None, help="synthetic extent (S, or H W in 2-D)")
-    ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--gap", type=int, default=1 if model == "upflow" else 2,
-                    help="the model runs on pairs (t, t+gap)" + ("" if model == "upflow" else ": a step spans gap / 2 frames"))
-    ap.add_argument("--model", default="train_log", help="directory holding the weights")
-    ap.add_argument("--batch", type=int, default=1, help="pairs per model call")
-    ap.add_argument("--direction", choices=("fwd", "bwd"), default="fwd",
-                    help="fwd: the flows t -> t+1; bwd: the model's own backward flows, from the last frame down")
-    ap.add_argument("--chunk", type=int, default=4, help="step flows estimated, labelled and linked at a time")
-    ap.add_argument("--spacing", type=float, nargs="+", default=[1.0], help="node spacing: one value or one per axis (%s)" % sp)
-    ap.add_argument("--dt", type=float, default=1.0, help="the time one frame spans: velocity = displacement / (frames spanned * dt)")
+    stepflows.add_source_args(ap, nd, model, direction="fwd: the flows t -> t+1; bwd: the model's own backward flows, from "
+                              "the last frame down", chunk="step flows estimated, labelled and linked at a time",
+                              dt="the time one frame spans: velocity = displacement / (frames spanned * dt)", spacing=True)
     ap.add_argument("--criterion", choices=("q", "l2", "both"), default="q",
                     help="foreground: q > 0, l2 < 0, or both (and every value finite)")
     ap.add_argument("--connectivity", choices=("face", "full"), default="face", help="face: 4 / 6 neighbours; full: 8 / 26")
@@ -275,26 +259,14 @@ def _args(nd, desc, model):
     ap.add_argument("--out", default=None, metavar="L.npy", help="write the dense labels [K, %s] (int32) here" % sp)
     ap.add_argument("--track-ids", default=None, metavar="T.npy", help="write every node's track id [K, %s] (int32) here" % sp)
     ap.add_argument("--save-flows", default=None, metavar="FLOWS.npy", help="write the step flows [K, %d, %s] here (--flows reads them)" % (nd, sp))
-    ap.add_argument("--json", default=None, help="write the report as JSON here")
-    ap.set_defaults(nd=nd)
     return ap
 
 
 def check_args(args):
     """What the parser cannot express."""
-    if sum(x is not None for x in (args.dataset, args.seq, args.flows)) == 0:
-        raise SystemExit("one of --dataset, --seq and --flows is needed")
-    if args.dataset and args.seq:
-        raise SystemExit("--dataset and --seq exclude each other")
-    for name in ("chunk", "batch", "min_size"):
-        if getattr(args, name) < 1:
-            raise SystemExit("--%s must be >= 1" % name.replace("_", "-"))
-    if args.start < 0:
-        raise SystemExit("--start must be >= 0")
-    if not (0 < args.dt < float("inf")):
-        raise SystemExit("--dt must be finite and positive")
-    if len(args.spacing) not in (1, args.nd) or not all(0 < h < float("inf") for h in args.spacing):
-        raise SystemExit("--spacing takes one or %d finite positive values" % args.nd)
+    stepflows.check_source_args(args)
+    if args.min_size < 1:
+        raise SystemExit("--min-size must be >= 1")
     if not (0.0 <= args.min_overlap <= 1.0):
         raise SystemExit("--min-overlap must lie in [0, 1]")
     if args.mask:
@@ -335,33 +307,9 @@ def _jsonable(v):
 def run(args, nd, model, make_model):
     """The regions of one parsed command line.  make_model() -> flows(frames, pairs) -> [2P, C, *sp]."""
     dev = torch.device("cuda")
-    frames = None
-    name = args.dataset or os.path.basename(args.seq or args.flows.rstrip("/"))
-    if args.dataset:
-        frames, _ = flow_eval.motion(args.dataset, args.frames, args.size, args.seed, dev)
-    elif args.seq:
-        frames = torch.from_numpy(np.load(args.seq).astype(np.float32)).to(dev)
-        if frames.dim() != nd + 1:
-            raise SystemExit("--seq must be [T,%s], got %s" % (",".join("DHW"[3 - nd:]), tuple(frames.shape)))
-    if args.flows:
-        visited, load, sp = trace._given_flows(args, nd)
-        source = lambda j0, j1: torch.from_numpy(load(j0, j1)).to(dev)
-    else:
-        sp = tuple(int(s) for s in frames.shape[1:])
-        chain = trace.step_chain(frames.shape[0], args.gap, args.direction, model)
-        visited = ([chain[0][0]] + [c[1] for c in chain]) if chain else []
-        if model == "rife":
-            pairs = flow_eval.rife_pairs(frames.shape[0], args.gap)
-        else:
-            pairs = [(t, t + args.gap) for t in range(0, frames.shape[0] - args.gap)]
-        flows_of = make_model() if chain else None
-
-        def source(j0, j1):
-            part = chain[j0:j1]
-            stack = flows_of(frames, [pairs[c[2] // 2] for c in part])
-            return stack[part[0][2] % 2::2]
-    n_flows = max(0, len(visited) - 1)
-    K = n_flows
+    sf = stepflows.open_step_flows(args, nd, model, make_model, dev)
+    name, sp, visited, source = sf.name, sf.sp, sf.visited, sf.source
+    K = n_flows = sf.n_steps
     masks = None
     if args.mask:
         m = np.load(args.mask, mmap_mode="r")
@@ -403,43 +351,19 @@ def run(args, nd, model, make_model):
         n_ev = {e: sum(1 for x in g["events"] if x["event"] == e) for e in EVENTS}
         print("%d tracks  %s" % (len(g["tracks"]), "  ".join("%s %d" % (e, n_ev[e]) for e in EVENTS)))
         print("flows %.3f s  kernel %.4f s" % (res["time_flows_s"], res["time_kernel_s"]))
-    for path in (args.out, args.track_ids, args.save_flows, args.json):
-        if path:
-            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    if args.out:
-        np.save(args.out, res["labels"].numpy())
-    if args.track_ids:
-        np.save(args.track_ids, res["track_ids"].numpy())
-    if args.save_flows:
-        np.save(args.save_flows, torch.cat(saved).numpy() if saved else np.zeros((0, nd) + sp, np.float32))
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(doc, f, indent=1)
+    stepflows.write_report(doc, args.json, {
+        args.out: lambda: res["labels"].numpy(), args.track_ids: lambda: res["track_ids"].numpy(),
+        args.save_flows: lambda: torch.cat(saved).numpy() if saved else np.zeros((0, nd) + sp, np.float32)})
     return doc
 
 
 def main_rife(Model, nd, argv=None):
     """flow2d / flow3d: the steps m -> m+h (or back) of the final IFNet flows."""
     args = check_args(_args(nd, "Vortex regions of the flows of a RIFE model, labelled and tracked", "rife").parse_args(argv))
-
-    def make_model():
-        m = Model(-1, device=torch.device("cuda"))
-        try:
-            m.load_model("flownet.pkl", args.model)
-        except FileNotFoundError:
-            print("no flownet.pkl under %s: using random-init weights" % args.model)
-        m.eval()
-        return lambda frames, pairs: flow_eval.rife_flows(m, frames, pairs, args.batch)
-
-    return run(args, nd, "rife", make_model)
+    return run(args, nd, "rife", stepflows.rife_model(Model, args))
 
 
 def main_upflow(make_net, argv=None):
     """upflow: the steps t -> t+gap through flow_f_out, or back through flow_b_out."""
     args = check_args(_args(2, "Vortex regions of UPFlow's flows, labelled and tracked", "upflow").parse_args(argv))
-
-    def make_model():
-        net = make_net(args.model)
-        return lambda frames, pairs: flow_eval.upflow_flows(net, frames, pairs, args.batch)
-
-    return run(args, 2, "upflow", make_model)
+    return run(args, 2, "upflow", stepflows.upflow_model(make_net, args))

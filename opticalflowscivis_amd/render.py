@@ -26,7 +26,6 @@ Out of scope: gradient shading; depth output; label and categorical volumes; sev
 interactive viewer.  Isosurface extraction -- the geometry behind an `iso:<value>` picture, as triangle meshes -- is
 opticalflowscivis_amd/isosurface.py (`flow3d.isosurface`)."""
 import argparse
-import json
 import math
 import os
 import struct
@@ -37,6 +36,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .stepflows import write_report
 
 PRESETS = ("grey", "hot", "coolwarm", "iso:<value>")
 
@@ -296,7 +296,7 @@ def _args(nd, desc):
     return ap
 
 
-def _source(args, nd):
+def series_source(args, nd):
     """(memory-mapped array, frame j -> its [*sp] block) of --seq or --field."""
     if (args.seq is None) == (args.field is None) and not (nd == 2 and args.flows and not args.seq and not args.field):
         raise SystemExit("exactly one of --seq and --field is needed")
@@ -335,19 +335,20 @@ def _value_range(args, take, K):
     return float(lo), float(hi)
 
 
-def _write(args, images, doc):
-    for path in (args.out, args.json):
-        if path:
-            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    if args.out and images is not None:
-        np.save(args.out, images)
+def _write(args, doc, images, pics=None):
+    """--png-dir gets frame_%04d.png of `images` and flow_%04d.png of `pics`, --out the images and, beside it as
+    <out>_flows.npy, the flow pictures, --json the report."""
     if args.png_dir:
         os.makedirs(args.png_dir, exist_ok=True)
-        for j, img in enumerate(images if images is not None else []):
-            write_png(os.path.join(args.png_dir, "frame_%04d.png" % j), to_uint8(img))
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(doc, f, indent=1)
+        for stem, stack in (("frame", images), ("flow", pics)):
+            for j, img in enumerate(stack if stack is not None else []):
+                write_png(os.path.join(args.png_dir, "%s_%04d.png" % (stem, j)), to_uint8(img))
+    arrays = {}
+    if args.out and images is not None:
+        arrays[args.out] = images
+    if args.out and pics is not None:
+        arrays[os.path.splitext(args.out)[0] + "_flows.npy"] = pics
+    write_report(doc, args.json, arrays)
 
 
 def main3d(argv=None):
@@ -357,7 +358,7 @@ def main3d(argv=None):
         raise SystemExit("--chunk and --image must be >= 1")
     if len(args.spacing) not in (1, 3) or not all(0 < h < float("inf") for h in args.spacing):
         raise SystemExit("--spacing takes one or 3 finite positive values")
-    a, take, name = _source(args, 3)
+    a, take, name = series_source(args, 3)
     K = int(a.shape[0])
     sp = tuple(int(s) for s in take(0, 1).shape[1:])
     spacing = args.spacing[0] if len(args.spacing) == 1 else tuple(args.spacing)
@@ -382,14 +383,14 @@ def main3d(argv=None):
     for w in res["frames"]:
         print("%s frame %d t %.4g: mean opacity %.4f  samples %d" % (name, w["frame"], w["time"], w["mean_opacity"], w["samples"]))
     print("load %.3f s  kernel %.4f s" % (res["time_load_s"], res["time_kernel_s"]))
-    _write(args, res["images"].numpy() if "images" in res else None, doc)
+    _write(args, doc, res["images"].numpy() if "images" in res else None)
     return doc
 
 
 def main2d(argv=None, desc="Colour-map a series of 2-D frames or fields; flow2rgb pictures of flows"):
     """flow2d / upflow: 2-D frames or fields through the transfer function in torch (no kernel), flows through flow2rgb."""
     args = _args(2, desc).parse_args(argv)
-    a, take, name = _source(args, 2)
+    a, take, name = series_source(args, 2)
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     doc = {"source": name, "tf": args.tf, "frames": [], "flows": None}
     images = None
@@ -414,12 +415,6 @@ def main2d(argv=None, desc="Colour-map a series of 2-D frames or fields; flow2rg
             raise SystemExit("--flows must be [K,2,H,W], got %s" % (fl.shape,))
         pics = np.stack([flow2rgb(np.moveaxis(np.asarray(f, np.float32), 0, -1), args.flow_base) for f in fl])
         doc["flows"] = {"source": os.path.basename(args.flows), "count": int(fl.shape[0]), "base": args.flow_base}
-    _write(args, images, doc)
-    if pics is not None:
-        if args.out:
-            np.save(os.path.splitext(args.out)[0] + "_flows.npy", pics)
-        if args.png_dir:
-            for j, p in enumerate(pics):
-                write_png(os.path.join(args.png_dir, "flow_%04d.png" % j), to_uint8(p))
+    _write(args, doc, images, pics)
     print("%s: %d frames, %s flow pictures" % (name or args.flows, len(doc["frames"]), doc["flows"]["count"] if doc["flows"] else 0))
     return doc

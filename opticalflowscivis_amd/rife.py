@@ -163,6 +163,18 @@ class ModelBase:
         return step
 
 
+def load_pretrained(Model, directory, device):
+    """A single-process `Model` on `device`, in eval mode, with the weights of `directory`/flownet.pkl -- or, said on
+    stdout, with random-init weights when there is no such file."""
+    model = Model(-1, device=device)
+    try:
+        model.load_model("flownet.pkl", directory)
+    except FileNotFoundError:
+        print("no flownet.pkl under %s: using random-init weights" % directory)
+    model.eval()
+    return model
+
+
 class UnsupLoss(collections.namedtuple(
         "UnsupLoss", "photo census smooth census_radius census_q smooth_kappa charb_q charb_eps",
         defaults=(0., 0., 0., 1, 0.4, 0., 0.25, 1e-9))):

@@ -7,11 +7,9 @@ entry points:
     python -m opticalflowscivis_amd.flow2d.trace --flows flows/ --start 1 --seeds seeds.npy --method rk4 --out traj.npy
     python -m opticalflowscivis_amd.upflow.trace --dataset rectangle2d --direction bwd --seed-grid 8 --json r.json
 
-The step flows come from the flows flow_eval already extracts (step_chain is pure index arithmetic over them).  A RIFE
-model run on the pairs (t, t+g), g = 2h, yields flows that start at each pair's mid frame, so the chain visits the frames
-h, 2h, 3h, ... for which both rife_consistency_pairs flows exist: forward in time through the flows m -> m+h (F_mid->1
-of pair m-h, on frame m's grid), backward through m+h -> m (F_mid->0 of pair m, on frame m+h's grid).  UPFlow gives
-t -> t+g and t+g -> t directly.  Tracing backward therefore uses the model's own backward flows with scale +1, not
+The step flows come from the flows flow_eval already extracts (stepflows.step_chain is pure index arithmetic over them;
+opticalflowscivis_amd/stepflows.py opens them for this tool, `ftle`, `vortex` and `regions` alike, and says which
+frames a RIFE and a UPFlow chain visit).  Tracing backward uses the model's own backward flows with scale +1, not
 negated forward ones.  --flows skips the model: a [K,C,*sp] .npy of consecutive step flows, or a directory of
 flow_%03d_to_%03d.npy files as --save-flows writes them, chained from --start.
 
@@ -27,68 +25,12 @@ FTLE fields, the derivative of the flow map reduced to Lyapunov exponents, are o
 entry points).  Out of scope: batches of several series in one launch; interleaved ([*sp, C]) flow layouts; autograd
 through the op."""
 import argparse
-import json
-import os
-import re
 import time
 
 import numpy as np
 import torch
 
-from . import flow_eval, ops
-
-
-def step_chain(T, gap, direction="fwd", model="rife"):
-    """[(t_from, t_to, index)] of the consecutive steps a trace takes through a series of T frames; `index` is the row
-    of the step's flow in the [2P, C, *sp] stack that flow_eval.rife_flows gives for rife_pairs(T, gap) (model="rife":
-    pair index // 2, flow index % 2) or flow_eval.upflow_flows for the pairs (t, t+gap) (model="upflow").  Forward:
-    ascending frames; backward: the same frames from the last one down, through the opposite flows.  Empty when the
-    series is too short."""
-    if direction not in ("fwd", "bwd"):
-        raise ValueError("direction must be 'fwd' or 'bwd', got %r" % (direction,))
-    if model == "rife":
-        by_start = {a: (b, i_f, i_b) for a, b, i_f, i_b in flow_eval.rife_consistency_pairs(T, gap)}
-        m = gap // 2
-    elif model == "upflow":
-        if gap < 1:
-            raise ValueError("gap must be >= 1, got %d" % gap)
-        by_start = {t: (t + gap, 2 * i, 2 * i + 1) for i, t in enumerate(range(0, T - gap))}
-        m = 0
-    else:
-        raise ValueError("model must be 'rife' or 'upflow', got %r" % (model,))
-    fwd, bwd = [], []
-    while m in by_start:
-        b, i_f, i_b = by_start[m]
-        fwd.append((m, b, i_f))
-        bwd.append((b, m, i_b))
-        m = b
-    return fwd if direction == "fwd" else bwd[::-1]
-
-
-_FLOW_FILE = re.compile(r"^flow_(\d+)_to_(\d+)\.npy$")
-
-
-def chain_flow_files(dirname, start, direction="fwd"):
-    """[(t_from, t_to, path)]: the flow_%03d_to_%03d.npy files of `dirname` chained from frame `start`: from each frame
-    the file that leads to the nearest later (fwd) / earlier (bwd) frame, until none does."""
-    if direction not in ("fwd", "bwd"):
-        raise ValueError("direction must be 'fwd' or 'bwd', got %r" % (direction,))
-    nxt = {}
-    for name in sorted(os.listdir(dirname)):
-        m = _FLOW_FILE.match(name)
-        if not m:
-            continue
-        a, b = int(m.group(1)), int(m.group(2))
-        if (b > a) != (direction == "fwd") or a == b:
-            continue
-        if a not in nxt or abs(b - a) < abs(nxt[a][0] - a):
-            nxt[a] = (b, os.path.join(dirname, name))
-    chain, t = [], int(start)
-    while t in nxt:
-        b, path = nxt[t]
-        chain.append((t, b, path))
-        t = b
-    return chain
+from . import flow_eval, ops, stepflows
 
 
 def trace_series(step_flows, n_steps, seeds, chunk=4, method="euler", substeps=1, scale=1.0, record=True):
@@ -160,39 +102,23 @@ def drift(a, b, frames):
 def _args(nd, desc, model):
     sp = ",".join("DHW"[3 - nd:])
     ap = argparse.ArgumentParser(description=desc)
-    ap.add_argument("--dataset", choices=flow_eval.DATASETS[nd], help="synthetic sequence with known motion")
-    ap.add_argument("--seq", help=".npy sequence [T,%s] in [0,1]" % sp)
+    stepflows.add_source_args(ap, nd, model, direction="trace forward or backward in time",
+                              chunk="step flows estimated at a time and advected in one launch")
     ap.add_argument("--gt", help=".npy per-frame velocities [T,%d,%s]: also trace the known motion, report the drift" % (nd, sp))
-    ap.add_argument("--flows", metavar="PATH", help="skip the model: a [K,%d,%s] .npy of consecutive step flows, or a "
-                    "directory of flow_%%03d_to_%%03d.npy files chained from --start" % (nd, sp))
-    ap.add_argument("--start", type=int, default=0, help="first frame of a --flows trace")
-    ap.add_argument("--frames", type=int, default=9, help="frames of a synthetic sequence")
-    ap.add_argument("--size", type=int, nargs="+", default=None, help="synthetic extent (S, or H W in 2-D)")
-    ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--gap", type=int, default=1 if model == "upflow" else 2,
-                    help="the model runs on pairs (t, t+gap)" + ("" if model == "upflow" else ": a step spans gap / 2 frames"))
-    ap.add_argument("--model", default="train_log", help="directory holding the weights")
-    ap.add_argument("--batch", type=int, default=1, help="pairs per model call")
     seeds = ap.add_mutually_exclusive_group(required=True)
     seeds.add_argument("--seeds", metavar="FILE", help=".npy seed positions [P,%d] as (x, y%s), in elements" % (nd, ", z" if nd == 3 else ""))
     seeds.add_argument("--seed-grid", type=int, metavar="STRIDE", help="seed every STRIDE-th element (1: the dense flow map)")
-    ap.add_argument("--direction", choices=("fwd", "bwd"), default="fwd", help="trace forward or backward in time")
     ap.add_argument("--method", choices=sorted(ops._ADV_METHODS), default="euler")
     ap.add_argument("--substeps", type=int, default=1)
-    ap.add_argument("--chunk", type=int, default=4, help="step flows estimated at a time and advected in one launch")
     ap.add_argument("--out", default=None, metavar="TRAJ.npy", help="write the trajectories [K+1,P,%d] (fp32) here" % nd)
     ap.add_argument("--map-out", default=None, metavar="MAP.npy",
                     help="write last position minus seed as a displacement [%d,%s] (needs --seed-grid 1)" % (nd, sp))
-    ap.add_argument("--json", default=None, help="write the report as JSON here")
     return ap
 
 
 def check_args(args):
     """What the parser cannot express."""
-    if sum(x is not None for x in (args.dataset, args.seq, args.flows)) == 0:
-        raise SystemExit("one of --dataset, --seq and --flows is needed")
-    if args.dataset and args.seq:
-        raise SystemExit("--dataset and --seq exclude each other")
+    stepflows.check_source_args(args)
     if args.dataset and args.gt:
         raise SystemExit("--gt goes with --seq or --flows: a --dataset carries its own known motion")
     if args.map_out and args.seed_grid != 1:
@@ -201,67 +127,14 @@ def check_args(args):
         raise SystemExit("--seed-grid must be >= 1")
     if args.substeps < 1:
         raise SystemExit("--substeps must be >= 1")
-    if args.chunk < 1:
-        raise SystemExit("--chunk must be >= 1")
-    if args.start < 0:
-        raise SystemExit("--start must be >= 0")
     return args
-
-
-def _given_flows(args, nd):
-    """(visited frames, step_flows(j0, j1, device), spatial shape) of --flows."""
-    if os.path.isdir(args.flows):
-        chain = chain_flow_files(args.flows, args.start, args.direction)
-        if not chain:
-            raise SystemExit("no flow_%03d_to_*.npy file in %s leads %s from frame %d" % (
-                args.start, args.flows, "forward" if args.direction == "fwd" else "backward", args.start))
-        frames = [chain[0][0]] + [c[1] for c in chain]
-        first = np.load(chain[0][2])
-        if first.ndim != nd + 1 or first.shape[0] != nd:
-            raise SystemExit("%s must be [%d,%s], got %s" % (chain[0][2], nd, ",".join("DHW"[3 - nd:]), first.shape))
-        load = lambda j0, j1: np.stack([np.load(c[2]).astype(np.float32) for c in chain[j0:j1]])
-        return frames, load, tuple(first.shape[1:])
-    arr = np.load(args.flows, mmap_mode="r")
-    if arr.ndim != nd + 2 or arr.shape[1] != nd or arr.shape[0] < 1:
-        raise SystemExit("--flows must be [K,%d,%s], got %s" % (nd, ",".join("DHW"[3 - nd:]), arr.shape))
-    sgn = 1 if args.direction == "fwd" else -1
-    frames = [args.start + sgn * j for j in range(arr.shape[0] + 1)]
-    if min(frames) < 0:
-        raise SystemExit("a backward trace through %d flows needs --start >= %d" % (arr.shape[0], arr.shape[0]))
-    return frames, (lambda j0, j1: np.array(arr[j0:j1], dtype=np.float32)), tuple(arr.shape[2:])
 
 
 def run(args, nd, model, make_model):
     """The trace of one parsed command line.  make_model() -> flows(frames, pairs) -> [2P, C, *sp]."""
     dev = torch.device("cuda")
-    frames = gt = None
-    name = args.dataset or os.path.basename(args.seq or args.flows.rstrip("/"))
-    if args.dataset:
-        frames, gt = flow_eval.motion(args.dataset, args.frames, args.size, args.seed, dev)
-    elif args.seq:
-        frames = torch.from_numpy(np.load(args.seq).astype(np.float32)).to(dev)
-        if frames.dim() != nd + 1:
-            raise SystemExit("--seq must be [T,%s], got %s" % (",".join("DHW"[3 - nd:]), tuple(frames.shape)))
-    if args.flows:
-        visited, load, sp = _given_flows(args, nd)
-        if frames is not None and tuple(frames.shape[1:]) != sp:
-            raise SystemExit("the flows' extent %s is not the series' %s" % (sp, tuple(frames.shape[1:])))
-        source = lambda j0, j1: torch.from_numpy(load(j0, j1)).to(dev)
-    else:
-        sp = tuple(int(s) for s in frames.shape[1:])
-        chain = step_chain(frames.shape[0], args.gap, args.direction, model)
-        visited = ([chain[0][0]] + [c[1] for c in chain]) if chain else []
-        if model == "rife":
-            pairs = flow_eval.rife_pairs(frames.shape[0], args.gap)
-        else:
-            pairs = [(t, t + args.gap) for t in range(0, frames.shape[0] - args.gap)]
-        flows_of = make_model() if chain else None
-
-        def source(j0, j1):
-            # the chain's flows of one direction share their parity in the model's (first, second) flow stack
-            part = chain[j0:j1]
-            stack = flows_of(frames, [pairs[c[2] // 2] for c in part])
-            return stack[part[0][2] % 2::2]
+    sf = stepflows.open_step_flows(args, nd, model, make_model, dev)
+    name, gt, sp, visited, K = sf.name, sf.gt, sf.sp, sf.visited, sf.n_steps
     if args.gt:
         vel = torch.from_numpy(np.load(args.gt).astype(np.float32)).to(dev)
         if vel.dim() != nd + 2 or tuple(vel.shape[1:]) != (nd,) + sp or (visited and vel.shape[0] <= max(visited[:-1] or [0])):
@@ -275,10 +148,9 @@ def run(args, nd, model, make_model):
         seeds = torch.from_numpy(np.ascontiguousarray(s.astype(np.float32).T)).to(dev)
     else:
         seeds = ops.grid_seeds(sp, args.seed_grid, 0, dev)
-    K = max(0, len(visited) - 1)
     record = args.out is not None or (gt is not None and not args.map_out)
     kw = dict(chunk=args.chunk, method=args.method, substeps=args.substeps, record=record)
-    res = trace_series(source, K, seeds, **kw)
+    res = trace_series(sf.source, K, seeds, **kw)
     doc = {"sequence": name, "shape": list(sp), "model": None if args.flows else args.model, "direction": args.direction,
            "method": args.method, "substeps": args.substeps, "chunk": args.chunk, "gap": args.gap,
            "frames": visited, "n_particles": int(seeds.shape[1]),
@@ -300,41 +172,19 @@ def run(args, nd, model, make_model):
             d = doc["drift"]["steps"][-1]
             line += "  | drift mean %.4f max %.4f over %d" % (d["mean"], d["max"], d["n"])
         print(line + "  | flows %.3f s  advection %.4f s" % (res["time_flows_s"], res["time_advect_s"]))
-    for path in (args.out, args.map_out, args.json):
-        if path:
-            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    if args.out:
-        np.save(args.out, res["traj"].permute(0, 2, 1).contiguous().cpu().numpy())
-    if args.map_out:
-        np.save(args.map_out, (res["pos"] - seeds).view((nd,) + sp).cpu().numpy())
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(doc, f, indent=1)
+    stepflows.write_report(doc, args.json, {
+        args.out: lambda: res["traj"].permute(0, 2, 1).contiguous().cpu().numpy(),
+        args.map_out: lambda: (res["pos"] - seeds).view((nd,) + sp).cpu().numpy()})
     return doc
 
 
 def main_rife(Model, nd, argv=None):
     """flow2d / flow3d: the steps m -> m+h (or back) of the final IFNet flows."""
     args = check_args(_args(nd, "trace particles through the flows of a RIFE model", "rife").parse_args(argv))
-
-    def make_model():
-        m = Model(-1, device=torch.device("cuda"))
-        try:
-            m.load_model("flownet.pkl", args.model)
-        except FileNotFoundError:
-            print("no flownet.pkl under %s: using random-init weights" % args.model)
-        m.eval()
-        return lambda frames, pairs: flow_eval.rife_flows(m, frames, pairs, args.batch)
-
-    return run(args, nd, "rife", make_model)
+    return run(args, nd, "rife", stepflows.rife_model(Model, args))
 
 
 def main_upflow(make_net, argv=None):
     """upflow: the steps t -> t+gap through flow_f_out, or back through flow_b_out."""
     args = check_args(_args(2, "trace particles through UPFlow's flows", "upflow").parse_args(argv))
-
-    def make_model():
-        net = make_net(args.model)
-        return lambda frames, pairs: flow_eval.upflow_flows(net, frames, pairs, args.batch)
-
-    return run(args, 2, "upflow", make_model)
+    return run(args, 2, "upflow", stepflows.upflow_model(make_net, args))

@@ -7,7 +7,7 @@ vorticity, the Q criterion and lambda2 (ops.velgrad: one launch per `--chunk` of
     python -m opticalflowscivis_amd.flow2d.vortex --flows flows.npy --fields vort,q --spacing 0.5 1.0 --out vg.npy
     python -m opticalflowscivis_amd.upflow.vortex --dataset rectangle2d --json r.json
 
-The step flows are those of `trace` (trace.step_chain over the flows flow_eval extracts, or --flows).  --out holds
+The step flows are those of `trace` (stepflows.step_chain over the flows flow_eval extracts, or --flows).  --out holds
 [K, NP, *sp] fp32 with the selected fields' planes in the order div, vort (1 plane in 2-D, 3 in 3-D), vmag, q, l2, grad
 (C * C planes, d u_r / d x_c at r * C + c); --mask holds the flags [K, *sp] uint8: bit 0 q > 0, bit 1 l2 < 0 (the two
 vortex criteria), bit 7 a value was not finite (every plane is NaN there).  For data from incompressible simulations the
@@ -23,25 +23,13 @@ swirling strength and the Delta criterion; eigenvectors; vortex core lines; a va
 Pictures of --out: opticalflowscivis_amd/render.py (the `render` entry points take the file as --field, --plane picks the
 field)."""
 import argparse
-import json
-import os
 import time
 
 import numpy as np
 import torch
 
-from . import flow_eval, ops, trace
-
-
-def step_scales(frames, dt):
-    """1 / (frames spanned * dt) for every step of a chain that visits `frames`."""
-    dt = float(dt)
-    if not (0 < dt < float("inf")):
-        raise ValueError("dt must be finite and positive, got %r" % (dt,))
-    spans = [abs(b - a) for a, b in zip(frames[:-1], frames[1:])]
-    if any(s == 0 for s in spans):
-        raise ValueError("every step must span at least one frame, got the frames %r" % (list(frames),))
-    return [1.0 / (s * dt) for s in spans]
+from . import ops, stepflows
+from .stepflows import step_scales
 
 
 def vortex_series(step_flows, n_steps, sp, fields=ops.VG_DEFAULT, spacing=1.0, chunk=4, frames=None, dt=1.0,
@@ -103,48 +91,20 @@ def vortex_series(step_flows, n_steps, sp, fields=ops.VG_DEFAULT, spacing=1.0, c
 def _args(nd, desc, model):
     sp = ",".join("DHW"[3 - nd:])
     ap = argparse.ArgumentParser(description=desc)
-    ap.add_argument("--dataset", choices=flow_eval.DATASETS[nd], help="synthetic sequence with known motion")
-    ap.add_argument("--seq", help=".npy sequence [T,%s] in [0,1]" % sp)
-    ap.add_argument("--flows", metavar="PATH", help="skip the model: a [K,%d,%s] .npy of consecutive step flows, or a "
-                    "directory of flow_%%03d_to_%%03d.npy files chained from --start" % (nd, sp))
-    ap.add_argument("--start", type=int, default=0, help="first frame of a --flows chain")
-    ap.add_argument("--frames", type=int, default=9, help="frames of a synthetic sequence")
-    ap.add_argument("--size", type=int, nargs="+", default=None, help="synthetic extent (S, or H W in 2-D)")
-    ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--gap", type=int, default=1 if model == "upflow" else 2,
-                    help="the model runs on pairs (t, t+gap)" + ("" if model == "upflow" else ": a step spans gap / 2 frames"))
-    ap.add_argument("--model", default="train_log", help="directory holding the weights")
-    ap.add_argument("--batch", type=int, default=1, help="pairs per model call")
-    ap.add_argument("--direction", choices=("fwd", "bwd"), default="fwd",
-                    help="fwd: the flows t -> t+1; bwd: the model's own backward flows, from the last frame down")
-    ap.add_argument("--chunk", type=int, default=4, help="step flows estimated at a time and handed to one launch")
+    stepflows.add_source_args(ap, nd, model, direction="fwd: the flows t -> t+1; bwd: the model's own backward flows, from "
+                              "the last frame down", chunk="step flows estimated at a time and handed to one launch",
+                              dt="the time one frame spans: velocity = displacement / (frames spanned * dt)", spacing=True)
     ap.add_argument("--fields", default=",".join(ops.VG_DEFAULT),
                     help="comma-separated, out of %s" % ",".join(ops.VG_FIELDS))
-    ap.add_argument("--spacing", type=float, nargs="+", default=[1.0], help="node spacing: one value or one per axis (%s)" % sp)
-    ap.add_argument("--dt", type=float, default=1.0, help="the time one frame spans: velocity = displacement / (frames spanned * dt)")
     ap.add_argument("--out", default=None, metavar="F.npy", help="write the planes [K, NP, %s] (fp32) here" % sp)
     ap.add_argument("--mask", default=None, metavar="M.npy", help="write the flags [K, %s] (uint8) here" % sp)
     ap.add_argument("--save-flows", default=None, metavar="FLOWS.npy", help="write the step flows [K, %d, %s] here (--flows reads them)" % (nd, sp))
-    ap.add_argument("--json", default=None, help="write the report as JSON here")
-    ap.set_defaults(nd=nd)
     return ap
 
 
 def check_args(args):
     """What the parser cannot express."""
-    if sum(x is not None for x in (args.dataset, args.seq, args.flows)) == 0:
-        raise SystemExit("one of --dataset, --seq and --flows is needed")
-    if args.dataset and args.seq:
-        raise SystemExit("--dataset and --seq exclude each other")
-    for name in ("chunk", "batch"):
-        if getattr(args, name) < 1:
-            raise SystemExit("--%s must be >= 1" % name)
-    if args.start < 0:
-        raise SystemExit("--start must be >= 0")
-    if not (0 < args.dt < float("inf")):
-        raise SystemExit("--dt must be finite and positive")
-    if len(args.spacing) not in (1, args.nd) or not all(0 < h < float("inf") for h in args.spacing):
-        raise SystemExit("--spacing takes one or %d finite positive values" % args.nd)
+    stepflows.check_source_args(args)
     try:
         ops.velgrad_planes(args.fields, args.nd)
     except ValueError as e:
@@ -154,37 +114,10 @@ def check_args(args):
 
 def run(args, nd, model, make_model):
     """The fields of one parsed command line.  make_model() -> flows(frames, pairs) -> [2P, C, *sp]."""
-    dev = torch.device("cuda")
-    frames = None
-    name = args.dataset or os.path.basename(args.seq or args.flows.rstrip("/"))
-    if args.dataset:
-        frames, _ = flow_eval.motion(args.dataset, args.frames, args.size, args.seed, dev)
-    elif args.seq:
-        frames = torch.from_numpy(np.load(args.seq).astype(np.float32)).to(dev)
-        if frames.dim() != nd + 1:
-            raise SystemExit("--seq must be [T,%s], got %s" % (",".join("DHW"[3 - nd:]), tuple(frames.shape)))
-    if args.flows:
-        visited, load, sp = trace._given_flows(args, nd)
-        source = lambda j0, j1: torch.from_numpy(load(j0, j1)).to(dev)
-    else:
-        sp = tuple(int(s) for s in frames.shape[1:])
-        chain = trace.step_chain(frames.shape[0], args.gap, args.direction, model)
-        visited = ([chain[0][0]] + [c[1] for c in chain]) if chain else []
-        if model == "rife":
-            pairs = flow_eval.rife_pairs(frames.shape[0], args.gap)
-        else:
-            pairs = [(t, t + args.gap) for t in range(0, frames.shape[0] - args.gap)]
-        flows_of = make_model() if chain else None
-
-        def source(j0, j1):
-            # the chain's flows of one direction share their parity in the model's (first, second) flow stack: the
-            # strided view goes to the kernel as it is
-            part = chain[j0:j1]
-            stack = flows_of(frames, [pairs[c[2] // 2] for c in part])
-            return stack[part[0][2] % 2::2]
-    K = max(0, len(visited) - 1)
+    sf = stepflows.open_step_flows(args, nd, model, make_model, torch.device("cuda"))
+    name, sp, visited, K = sf.name, sf.sp, sf.visited, sf.n_steps
     spacing = args.spacing[0] if len(args.spacing) == 1 else tuple(args.spacing)
-    res = vortex_series(source, K, sp, args.fields, spacing, args.chunk, frames=visited or [0], dt=args.dt,
+    res = vortex_series(sf.source, K, sp, args.fields, spacing, args.chunk, frames=visited or [0], dt=args.dt,
                         keep_out=bool(args.out), keep_flags=bool(args.mask), keep_flows=bool(args.save_flows))
     planes = {n: [s.start, s.stop] for n, s in res["planes"].items()}
     doc = {"sequence": name, "shape": list(sp), "model": None if args.flows else args.model, "direction": args.direction,
@@ -199,43 +132,18 @@ def run(args, nd, model, make_model):
             w["frac_l2_neg"], w["frac_both"], w["n_nonfinite"]))
     if res["steps"]:
         print("flows %.3f s  kernel %.4f s" % (res["time_flows_s"], res["time_kernel_s"]))
-    for path in (args.out, args.mask, args.save_flows, args.json):
-        if path:
-            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    if args.out:
-        np.save(args.out, res["out"].numpy())
-    if args.mask:
-        np.save(args.mask, res["flags"].numpy())
-    if args.save_flows:
-        np.save(args.save_flows, res["flows"].numpy())
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(doc, f, indent=1)
+    stepflows.write_report(doc, args.json, {args.out: lambda: res["out"].numpy(), args.mask: lambda: res["flags"].numpy(),
+                                            args.save_flows: lambda: res["flows"].numpy()})
     return doc
 
 
 def main_rife(Model, nd, argv=None):
     """flow2d / flow3d: the steps m -> m+h (or back) of the final IFNet flows."""
     args = check_args(_args(nd, "Vortex and divergence fields of the flows of a RIFE model", "rife").parse_args(argv))
-
-    def make_model():
-        m = Model(-1, device=torch.device("cuda"))
-        try:
-            m.load_model("flownet.pkl", args.model)
-        except FileNotFoundError:
-            print("no flownet.pkl under %s: using random-init weights" % args.model)
-        m.eval()
-        return lambda frames, pairs: flow_eval.rife_flows(m, frames, pairs, args.batch)
-
-    return run(args, nd, "rife", make_model)
+    return run(args, nd, "rife", stepflows.rife_model(Model, args))
 
 
 def main_upflow(make_net, argv=None):
     """upflow: the steps t -> t+gap through flow_f_out, or back through flow_b_out."""
     args = check_args(_args(2, "Vortex and divergence fields of UPFlow's flows", "upflow").parse_args(argv))
-
-    def make_model():
-        net = make_net(args.model)
-        return lambda frames, pairs: flow_eval.upflow_flows(net, frames, pairs, args.batch)
-
-    return run(args, 2, "upflow", make_model)
+    return run(args, 2, "upflow", stepflows.upflow_model(make_net, args))

@@ -145,7 +145,7 @@ def test_k_steps_equal_k_single_steps():
 
 
 def test_step_chain():
-    from opticalflowscivis_amd.trace import step_chain
+    from opticalflowscivis_amd.stepflows import step_chain
     assert step_chain(7, 2, "fwd") == [(1, 2, 1), (2, 3, 3), (3, 4, 5), (4, 5, 7)]
     assert step_chain(7, 2, "bwd") == [(5, 4, 8), (4, 3, 6), (3, 2, 4), (2, 1, 2)]
     assert step_chain(9, 4, "fwd") == [(2, 4, 1), (4, 6, 5)]
@@ -170,7 +170,7 @@ def test_step_chain():
 
 
 def test_flow_directory_chaining(tmp_path):
-    from opticalflowscivis_amd.trace import chain_flow_files
+    from opticalflowscivis_amd.stepflows import chain_flow_files
     d = str(tmp_path)
     # what evaluate_flow --save-flows writes for a RIFE model at gap 2: mid -> t0 and mid -> t1 of every pair
     for a, b in ((1, 0), (1, 2), (2, 1), (2, 3), (3, 2), (3, 4), (3, 6)):
