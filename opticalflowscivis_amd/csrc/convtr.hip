@@ -708,6 +708,8 @@ __global__ __launch_bounds__(512, 2) void convtr_mfma16_ws_kernel(const float* _
 // item ahead of the matrix waves across brick boundaries.  A matrix wave owns one (z, y) position row of the 2x2
 // brick and NT position tiles of it.
 constexpr int p8_ws_ci(int rt) { return 128 * rt + 16; }  // floats per input channel (+16: LDS bank spread)
+// 4-byte words of the pre-split table (round 13): [chunk of 4 channels][row tile][piece 3] x 1 KB
+constexpr long long p8_split_words(int cinp, int rt) { return (long long)(cinp / 4) * rt * 768; }
 __host__ __device__ constexpr int p8_k(int par, int d) { return par == 0 ? (d == 0 ? 1 : 3) : (d == 0 ? 0 : 2); }
 
 #ifdef FS_TR_STAMPS
@@ -732,9 +734,33 @@ __global__ __launch_bounds__(512, 2) void convtr_p8_kernel(const float* __restri
   constexpr int WSCI = p8_ws_ci(RT);
   constexpr int NW = CINP * WSCI;                      // whole weight table
   constexpr int NWL = (NW + 255) / 256 * 256;
-  static_assert((NWL + 2 * NXL) * 4 <= 160 * 1024, "weights + two input buffers fit the CU's LDS");
   static_assert(NT % 2 == 1, "tiles are processed in pairs + one");
-  __shared__ __attribute__((aligned(16))) float lds[NWL + 2 * NXL];
+  // Round 13, the split-bf16 body (<= 32 input channels, <= 3 row tiles): v_mfma_f32_16x16x32_bf16, whose 32 reduction
+  // elements are exactly one chunk -- 8 neighbours x 4 channels; three bf16 pieces per operand and six products as in
+  // convtr_s3.hpp.  LDS, in bytes: the pre-split table [chunk][row tile][piece][kq][row 16][8 bf16] (FS_WPREP_P8 with
+  // split = 1, resident), two piece images [piece][z 3][y 3][x XP][4 channels] of a chunk's brick, and ONE raw staging area
+  // [(slot, loader wave)][channel 4][lane 64] x 16 bytes (two do not fit beside 72 KB of weights, and measured no faster
+  // where they do).
+  constexpr bool S3 = CINP == 32 && RT <= 3;
+  constexpr int S_ROWB = XP * 8;                    // one row of a piece image
+  constexpr int S_PIECEB = ZT * YT * S_ROWB + 64;   // (+64: the last tile's dropped columns read past the last row)
+  constexpr int S_IMGB = 3 * S_PIECEB;
+  constexpr int S_WTB = (CINP / CI) * RT * 3 * 1024;
+  constexpr int S_NQ = XP / 4;                      // 16-byte pieces per row and channel
+  constexpr int S_NITEM = ZT * YT * S_NQ;           // (row, piece) items of a brick, one per loader lane and slot
+  [[maybe_unused]] constexpr int S_NSLOT = (S_NITEM + 255) / 256;
+  constexpr int S_STGB = (S_NITEM + 63) / 64 * 4096;
+  constexpr int S_BYTES = S_WTB + 2 * S_IMGB + S_STGB;
+#ifdef FS_ABLATION
+  constexpr int LDSF = (S3 && S_BYTES / 4 > NWL + 2 * NXL) ? S_BYTES / 4 : NWL + 2 * NXL;
+  const bool s3 = S3 && !(p.ab & 256);  // FLOWSCI_TR_P8_NO_S3=1: the fp32 body these instantiations had before round 13
+#else
+  constexpr int LDSF = S3 ? S_BYTES / 4 : NWL + 2 * NXL;
+  constexpr bool s3 = S3;
+#endif
+  static_assert(LDSF * 4 <= 160 * 1024, "weights + the input stages fit the CU's LDS");
+  __shared__ __attribute__((aligned(16))) float lds[LDSF];
+  [[maybe_unused]] unsigned char* const ldsb = reinterpret_cast<unsigned char*>(lds);
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -752,6 +778,96 @@ __global__ __launch_bounds__(512, 2) void convtr_p8_kernel(const float* __restri
   if (wave >= 4) {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the host pass has neither the buffer-resource type nor the LDS-DMA builtin)
     __builtin_amdgcn_s_setprio(3);  // (a loader wave issues a handful of instructions per period: they should not queue behind the matrix wave's)
+    if constexpr (S3) {
+      if (s3) {
+        // ---- split body: lane = one (row, 16-byte piece) item per slot, all four channels of the chunk.  An item reaches
+        // the conversion through LDS (convtr_s3.hpp: why not through registers in flight): every wave copies its OWN items
+        // into its staging units and reads them back, so the loader waves need no barrier among themselves.
+        {  // the whole pre-split table, once (chunks past the layer's read as zero and are never used)
+          __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)Wt, (short)0, (p.Cin + 3) / 4 * RT * 3072, 0x00020000);
+#pragma unroll
+          for (int k = 0; k < S_WTB / 4096; ++k)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(ldsb + 1024 * (wv + 4 * k)), 16,
+                                                     (unsigned)(1024 * (wv + 4 * k) + 16 * lane), 0, 0, 0);
+        }
+        unsigned char* const stg = ldsb + S_WTB + 2 * S_IMGB;
+        const unsigned volB = (unsigned)(xvol * 4u);
+        unsigned xoff[S_NSLOT];
+        int b = 0;
+        auto offsets = [&](long long tile) {
+          int qz0, qy0, q0;
+          decode(tile, b, qz0, qy0, q0);
+#pragma unroll
+          for (int sl = 0; sl < S_NSLOT; ++sl) {
+            const int item = 256 * sl + 64 * wv + lane;
+            const int row = item / S_NQ, jq = item - row * S_NQ;
+            const int z = row / YT, y = row - z * YT;
+            const int gz = qz0 - 1 + z, gy = qy0 - 1 + y, gx = q0 - 4 + 4 * jq;
+            const bool ok = item < S_NITEM && gz >= 0 && gz < p.Di && gy >= 0 && gy < p.Hi && gx >= 0 && gx + 3 < p.Wi;
+            xoff[sl] = ok ? (((unsigned)gz * p.Hi + gy) * p.Wi + gx) * 4u : DMA_OOB;
+          }
+        };
+        auto stage = [&](int c0) {
+#pragma unroll
+          for (int c = 0; c < CI; ++c) {
+            const bool in = c0 + c < p.Cin;  // channels past Cin read as zero: an empty buffer
+            __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(X + ((size_t)b * p.Cin + (in ? c0 + c : 0)) * xvol), (short)0, in ? (int)volB : 0, 0x00020000);
+#pragma unroll
+            for (int sl = 0; sl < S_NSLOT; ++sl)
+              if (256 * sl + 64 * wv < S_NITEM)  // wave-uniform
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(stg + (4 * sl + wv) * 4096 + c * 1024), 16, xoff[sl], 0, 0, 0);
+          }
+        };
+        // the request stream runs one (brick, chunk) item ahead of the conversion, which runs one ahead of the matrix waves
+        // (two raw stages, where they fit, measured no faster: the conversion itself is the loaders' period)
+        long long rtile = t0;
+        int rc0 = 0;
+        auto request_next = [&]() {
+          if (rc0 + CI < p.Cin) rc0 += CI;
+          else if (rtile + 1 < t1) { ++rtile; rc0 = 0; offsets(rtile); }
+          else return;
+          stage(rc0);
+        };
+        auto take = [&](int buf) {  // the staged item -> registers, the next request, three pieces -> piece image `buf`
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          t3_u32x4 ld[S_NSLOT][4];
+#pragma unroll
+          for (int sl = 0; sl < S_NSLOT; ++sl)
+            if (256 * sl + 64 * wv < S_NITEM)
+#pragma unroll
+              for (int c = 0; c < CI; ++c)
+                ld[sl][c] = *reinterpret_cast<const t3_u32x4*>(stg + (4 * sl + wv) * 4096 + c * 1024 + 16 * lane);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+          request_next();  // (the staging units are free: this wave alone reads them, and has)
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int sl = 0; sl < S_NSLOT; ++sl)
+            if (256 * sl + 64 * wv < S_NITEM) {
+              const int item = 256 * sl + 64 * wv + lane;
+              const int row = item / S_NQ, jq = item - row * S_NQ;
+              if (item < S_NITEM) t3_split_store(ld[sl], ldsb + S_WTB + buf * S_IMGB + row * S_ROWB + jq * 32, S_PIECEB);
+            }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        };
+        if (t0 < t1) {
+          offsets(t0);
+          stage(0);
+          take(0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();  // weights and the first item's pieces are in place
+        int buf = 0;
+        for (long long tile = t0; tile < t1; ++tile)
+          for (int c0 = 0; c0 < p.Cin; c0 += CI) {
+            if (c0 + CI < p.Cin || tile + 1 < t1) take(buf ^ 1);
+            __builtin_amdgcn_s_barrier();
+            buf ^= 1;
+          }
+        return;
+      }
+    }
     constexpr int NXW = (NXL / 256 + 3) / 4, NWW = (NWL / 256 + 3) / 4;
     {  // the whole weight table (the layer's (Cin + 3) / 4 * 4 channels: the workspace holds no more), once
       __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)Wt, (short)0, (p.Cin + 3) / 4 * 4 * WSCI * 4,
@@ -840,41 +956,105 @@ __global__ __launch_bounds__(512, 2) void convtr_p8_kernel(const float* __restri
         for (int r = 0; r < 4; ++r) acc[rt][n][r] = 0.f;
 
     for (int c0 = 0; c0 < p.Cin; c0 += CI) {
-      // A operands of the chunk: W'[c0 + kq][neighbour d][row = 16 rt + (lane & 15)]
-      const float* aB = lds + (size_t)(c0 + kq) * WSCI + col;
-      float av[8][RT];
+      bool done = false;
+      if constexpr (S3) {
+        if (s3) {
+          // A: one ds_read_b128 per (row tile, piece) -- the lane's (dz, dy) pair kq, row lane & 15: 4 channels at x
+          // neighbours q - 1, q.  B: the same 8 values of position col of tile n, two 8-byte reads of a piece image
+          const unsigned char* wt = ldsb + (c0 / CI) * RT * 3072 + 16 * lane;
+          t3_bf16x8 a[RT][3];
 #pragma unroll
-      for (int d = 0; d < 8; ++d)
+          for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) av[d][rt] = aB[(d * RT + rt) * 16];
-      const float* bB = lds + bBo + buf * NXL;
-      // B operands: the 2x2x2 neighbourhood {q, q-1}^3 of two position tiles, read one tile pair ahead of the MFMAs
-      float xa[2][8], xb[2][8];
-      auto load_x = [&](int n, float (&xn)[8]) {
+            for (int pc = 0; pc < 3; ++pc)
+              a[rt][pc] = __builtin_bit_cast(t3_bf16x8, *reinterpret_cast<const t3_u32x4*>(wt + (rt * 3 + pc) * 1024));
+          const unsigned char* img = ldsb + S_WTB + buf * S_IMGB +
+                                     (((wz + 1 - (kq >> 1)) * YT + (wy + 1 - (kq & 1))) * XP + col + 3) * 8;
+          auto load_b = [&](int n, t3_bf16x8 (&bq)[3]) {
 #pragma unroll
-        for (int d = 0; d < 8; ++d) xn[d] = bB[16 * n - ((d >> 2) & 1) * PS - ((d >> 1) & 1) * XP - (d & 1)];
-      };
-      // two tiles at a time: consecutive MFMAs go to different accumulators (40-cycle dependent latency)
-      auto mma_pair = [&](int n, const float (&x0)[8], const float (&x1)[8], bool two) {
+            for (int pc = 0; pc < 3; ++pc) {
+              const unsigned char* q = img + pc * S_PIECEB + n * 128;
+              const t3_u32x2 lo = *(t3_lds_v64)(lds_ptr_t)q, hi = *(t3_lds_v64)(lds_ptr_t)(q + 8);  // (volatile: never paired, convtr_s3.hpp)
+              const t3_u32x4 v = {lo.x, lo.y, hi.x, hi.y};
+              bq[pc] = __builtin_bit_cast(t3_bf16x8, v);
+            }
+          };
+          // two tiles and all row tiles at a time: consecutive MFMAs go to different accumulators
+          auto mma_pair = [&](int n, const t3_bf16x8 (&b0)[3], const t3_bf16x8 (&b1)[3], bool two) {
+#pragma unroll
+            for (int q6 = 0; q6 < 6; ++q6)
+#pragma unroll
+              for (int rt = 0; rt < RT; ++rt) {
+                acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[rt][T3_PA[q6]], b0[T3_PB[q6]], acc[rt][n], 0, 0, 0);
+                if (two) acc[rt][n + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[rt][T3_PA[q6]], b1[T3_PB[q6]], acc[rt][n + 1], 0, 0, 0);
+              }
+          };
+          t3_bf16x8 ba[2][3], bb[2][3];
+          load_b(0, ba[0]);
+          if (NT > 1) load_b(1, ba[1]);
+#pragma unroll
+          for (int n = 0; n < NT; n += 4) {
+            if (n + 2 < NT) { load_b(n + 2, bb[0]); if (n + 3 < NT) load_b(n + 3, bb[1]); }
+            __builtin_amdgcn_sched_barrier(0);
+            mma_pair(n, ba[0], ba[1], n + 1 < NT);
+            if (n + 2 < NT) {
+              if (n + 4 < NT) { load_b(n + 4, ba[0]); if (n + 5 < NT) load_b(n + 5, ba[1]); }
+              __builtin_amdgcn_sched_barrier(0);
+              mma_pair(n + 2, bb[0], bb[1], n + 3 < NT);
+            }
+          }
+          done = true;
+        }
+      }
+      if (!done) {
+        // A operands of the chunk: W'[c0 + kq][neighbour d][row = 16 rt + (lane & 15)]
+        const float* aB = lds + (size_t)(c0 + kq) * WSCI + col;
+        float av[8][RT];
 #pragma unroll
         for (int d = 0; d < 8; ++d)
 #pragma unroll
-          for (int rt = 0; rt < RT; ++rt) {
-            acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[d][rt], x0[d], acc[rt][n], 0, 0, 0);
-            if (two) acc[rt][n + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[d][rt], x1[d], acc[rt][n + 1], 0, 0, 0);
-          }
-      };
-      load_x(0, xa[0]);
-      if (NT > 1) load_x(1, xa[1]);
+          for (int rt = 0; rt < RT; ++rt) av[d][rt] = aB[(d * RT + rt) * 16];
+        const float* bB = lds + bBo + buf * NXL;
+        // B operands: the 2x2x2 neighbourhood {q, q-1}^3 of two position tiles, read one tile pair ahead of the MFMAs
+        float xa[2][8], xb[2][8];
+        auto load_x = [&](int n, float (&xn)[8]) {
 #pragma unroll
-      for (int n = 0; n < NT; n += 4) {
-        if (n + 2 < NT) { load_x(n + 2, xb[0]); if (n + 3 < NT) load_x(n + 3, xb[1]); }
-        __builtin_amdgcn_sched_barrier(0);
-        mma_pair(n, xa[0], xa[1], n + 1 < NT);
-        if (n + 2 < NT) {
-          if (n + 4 < NT) { load_x(n + 4, xa[0]); if (n + 5 < NT) load_x(n + 5, xa[1]); }
-          __builtin_amdgcn_sched_barrier(0);
-          mma_pair(n + 2, xb[0], xb[1], n + 3 < NT);
+          for (int d = 0; d < 8; ++d) xn[d] = bB[16 * n - ((d >> 2) & 1) * PS - ((d >> 1) & 1) * XP - (d & 1)];
+        };
+        // two tiles at a time: consecutive MFMAs go to different accumulators (40-cycle dependent latency)
+        auto mma_pair = [&](int n, const float (&x0)[8], const float (&x1)[8], bool two) {
+#pragma unroll
+          for (int d = 0; d < 8; ++d)
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+              acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[d][rt], x0[d], acc[rt][n], 0, 0, 0);
+              if (two) acc[rt][n + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[d][rt], x1[d], acc[rt][n + 1], 0, 0, 0);
+            }
+        };
+        if constexpr (RT == 6) {
+          // (one operand set: beside 120 accumulators and 48 A registers the second one spilled)
+#pragma unroll
+          for (int n = 0; n < NT; n += 2) {
+            load_x(n, xa[0]);
+            if (n + 1 < NT) load_x(n + 1, xa[1]);
+            __builtin_amdgcn_sched_barrier(0);
+            mma_pair(n, xa[0], xa[1], n + 1 < NT);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        } else {
+          load_x(0, xa[0]);
+          if (NT > 1) load_x(1, xa[1]);
+#pragma unroll
+          for (int n = 0; n < NT; n += 4) {
+            if (n + 2 < NT) { load_x(n + 2, xb[0]); if (n + 3 < NT) load_x(n + 3, xb[1]); }
+            __builtin_amdgcn_sched_barrier(0);
+            mma_pair(n, xa[0], xa[1], n + 1 < NT);
+            if (n + 2 < NT) {
+              if (n + 4 < NT) { load_x(n + 4, xa[0]); if (n + 5 < NT) load_x(n + 5, xa[1]); }
+              __builtin_amdgcn_sched_barrier(0);
+              mma_pair(n + 2, xb[0], xb[1], n + 3 < NT);
+            }
+          }
         }
       }
       TSTAMP(0);
@@ -1086,7 +1266,8 @@ extern "C" long long fs_conv3d_tr_ws_floats(int Cin, int Cout) {
   if (Cout > 32) Cout = 32;
   const long long cinp = (Cin + 3) / 4 * 4;
   // W'[ci][neighbour][row] (+ pad) of the all-parities kernel (<= 12 channels), or the slabs of the class kernels
-  const long long p8 = Cout <= 12 ? cinp * p8_ws_ci(Cout <= 2 ? 1 : (Cout <= 6 ? 3 : 6)) : 0;
+  long long p8 = Cout <= 12 ? cinp * p8_ws_ci(Cout <= 2 ? 1 : (Cout <= 6 ? 3 : 6)) : 0;
+  if (Cout <= 6 && cinp <= 32 && p8_split_words((int)cinp, Cout <= 2 ? 1 : 3) > p8) p8 = p8_split_words((int)cinp, Cout <= 2 ? 1 : 3);
   long long cls = Cout <= 6 ? 0 : cinp * 64 * (Cout <= 16 ? 16 : 32);
   if (Cout > 16 && t3_slab_words(Cin) > cls) cls = t3_slab_words(Cin);  // the split-bf16 slabs (convtr_s3.hpp)
   if (Cout <= 16 && t3_slab_words16(Cin) > cls) cls = t3_slab_words16(Cin);
@@ -1137,7 +1318,14 @@ static int conv3d_tr_slice(const float* x, const float* w, const float* bias, co
     p.tiles = (long long)B * p.tz * p.ty * p.tx;
     if (p.tiles >= 16 && p.tiles < (1ll << 31)) {
       const int cinp = (Cin + 3) / 4 * 4;
-      wprep_do(wprep_job(FS_WPREP_P8, w, ws, (long long)cinp * p8_ws_ci(rt), Cin, Cout, cinp, rt), plan, st);
+      // round 13: <= 32 input channels and <= 3 row tiles run on split-bf16 MFMAs, from a pre-split table
+      static const bool p8_no_s3 = FS_AB_ENV("FLOWSCI_TR_P8_NO_S3");
+      const bool split = Cin <= 32 && rt <= 3 && !p8_no_s3;
+#ifdef FS_ABLATION
+      if (!split) p.ab = 256;
+#endif
+      wprep_do(wprep_job(FS_WPREP_P8, w, ws, split ? p8_split_words(cinp, rt) : (long long)cinp * p8_ws_ci(rt), Cin, Cout, cinp, rt,
+                         split ? 1 : 0), plan, st);
       if (plan != nullptr) return FS_OK;
       if (Cin > 32) {  // block0's heads (64 input channels): the weight table is twice as large
         if (rt == 1) { if (wide) launch_p8<1, 9, 64>(x, ws, bias, y, p, st); else launch_p8<1, 5, 64>(x, ws, bias, y, p, st); }

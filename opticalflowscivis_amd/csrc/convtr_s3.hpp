@@ -48,6 +48,38 @@ inline long long t3_slab_words(int Cin) { return (long long)((Cin + 3) / 4) * T3
 constexpr int T3_WB16 = 8 * 3 * 1024;
 inline long long t3_slab_words16(int Cin) { return (long long)((Cin + 3) / 4) * (T3_WB16 / 4); }
 
+// the six products of a split-bf16 product a b = sum a_i b_j (i + j <= 2), small terms first: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
+constexpr int T3_PA[6] = {2, 0, 1, 1, 0, 0}, T3_PB[6] = {0, 2, 1, 0, 1, 0};
+
+// One loader item: four consecutive positions of the four channels of a stage (`ld[channel]`, 16 bytes each) -> three bf16
+// pieces (a = a0 + a1 + a2, each the rounding of what the ones before leave) -> the item's 32 bytes [position 4][channel 4]
+// of each piece image (`pieceb` bytes apart).  Shared by convtr_s3_kernel and the split body of convtr_p8_kernel.
+__device__ __forceinline__ void t3_split_store(const t3_u32x4 (&ld)[4], unsigned char* dst, int pieceb) {
+  const unsigned u[4][4] = {{ld[0].x, ld[0].y, ld[0].z, ld[0].w}, {ld[1].x, ld[1].y, ld[1].z, ld[1].w},
+                            {ld[2].x, ld[2].y, ld[2].z, ld[2].w}, {ld[3].x, ld[3].y, ld[3].z, ld[3].w}};
+  unsigned h[3][4][2];  // [piece][position][channel pair]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int cp = 0; cp < 2; ++cp) {
+      float ra = __uint_as_float(u[2 * cp][i]), rc = __uint_as_float(u[2 * cp + 1][i]);
+      h[0][i][cp] = s3_pack(ra, rc);
+      ra -= __uint_as_float(h[0][i][cp] << 16); rc -= __uint_as_float(h[0][i][cp] & 0xffff0000u);
+      asm volatile("" : "+v"(ra), "+v"(rc));  // (keeps the SLP vectoriser from pairing the subtractions)
+      h[1][i][cp] = s3_pack(ra, rc);
+      ra -= __uint_as_float(h[1][i][cp] << 16); rc -= __uint_as_float(h[1][i][cp] & 0xffff0000u);
+      asm volatile("" : "+v"(ra), "+v"(rc));
+      h[2][i][cp] = s3_pack(ra, rc);
+    }
+#pragma unroll
+  for (int pc = 0; pc < 3; ++pc) {
+    const t3_u32x4 v0 = {h[pc][0][0], h[pc][0][1], h[pc][1][0], h[pc][1][1]};
+    const t3_u32x4 v1 = {h[pc][2][0], h[pc][2][1], h[pc][3][0], h[pc][3][1]};
+    *reinterpret_cast<t3_u32x4*>(dst + pc * pieceb) = v0;
+    *reinterpret_cast<t3_u32x4*>(dst + pc * pieceb + 16) = v1;
+  }
+}
+
 // M16: the 16-row form for 7..16 output channels (the input gradient of conv0[0], 32 -> 11 / 12): v_mfma_f32_16x16x32_bf16,
 // whose 32 reduction elements are ALL eight taps of a class x 4 channels -- the lane quarter `kq` takes the (y tap, x tap)
 // pair, a lane's 8 values are the 4 channels at the two z taps (two ds_read_b64 of the same LDS image); a wave's 6 row tiles
@@ -178,32 +210,7 @@ __global__ __launch_bounds__(64 * (T3_NMW + T3_NLW), 1) void convtr_s3_kernel(co
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(dst + 1024 * i), 16, woff[k], 0, 0, 0);
       }
     };
-    auto convert = [&](int buf, const t3_u32x4 (&ld)[4]) {
-      unsigned char* dst = lds + buf * T3_INB + loff;
-      const unsigned u[4][4] = {{ld[0].x, ld[0].y, ld[0].z, ld[0].w}, {ld[1].x, ld[1].y, ld[1].z, ld[1].w},
-                                {ld[2].x, ld[2].y, ld[2].z, ld[2].w}, {ld[3].x, ld[3].y, ld[3].z, ld[3].w}};
-      unsigned h[3][4][2];  // [piece][position][channel pair]
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int cp = 0; cp < 2; ++cp) {
-          float ra = __uint_as_float(u[2 * cp][i]), rc = __uint_as_float(u[2 * cp + 1][i]);
-          h[0][i][cp] = s3_pack(ra, rc);
-          ra -= __uint_as_float(h[0][i][cp] << 16); rc -= __uint_as_float(h[0][i][cp] & 0xffff0000u);
-          asm volatile("" : "+v"(ra), "+v"(rc));  // (keeps the SLP vectoriser from pairing the subtractions)
-          h[1][i][cp] = s3_pack(ra, rc);
-          ra -= __uint_as_float(h[1][i][cp] << 16); rc -= __uint_as_float(h[1][i][cp] & 0xffff0000u);
-          asm volatile("" : "+v"(ra), "+v"(rc));
-          h[2][i][cp] = s3_pack(ra, rc);
-        }
-#pragma unroll
-      for (int pc = 0; pc < 3; ++pc) {
-        const t3_u32x4 v0 = {h[pc][0][0], h[pc][0][1], h[pc][1][0], h[pc][1][1]};
-        const t3_u32x4 v1 = {h[pc][2][0], h[pc][2][1], h[pc][3][0], h[pc][3][1]};
-        *reinterpret_cast<t3_u32x4*>(dst + pc * T3_PIECEB) = v0;
-        *reinterpret_cast<t3_u32x4*>(dst + pc * T3_PIECEB + 16) = v1;
-      }
-    };
+    auto convert = [&](int buf, const t3_u32x4 (&ld)[4]) { t3_split_store(ld, lds + buf * T3_INB + loff, T3_PIECEB); };
     // Iteration g of the stream (stage g % NS of brick g / NS) runs beside the matrix waves' stage g - 1 and ends in barrier
     // #g.  Only LDS-DMA copies are ever in flight here, and they complete in the order they were issued:
     //   vmcnt(0): the staged brick of stage g has landed (requested an iteration ago) -> the wave's items to registers;
@@ -301,7 +308,6 @@ __global__ __launch_bounds__(64 * (T3_NMW + T3_NLW), 1) void convtr_s3_kernel(co
           for (int pc = 0; pc < 3; ++pc)
             a[pc] = __builtin_bit_cast(t3_bf16x8, *reinterpret_cast<const t3_u32x4*>(sw + (px * 3 + pc) * 1024));
           read_b(px, 0, b0);
-          constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
           for (int i = 0; i < 2 * T3_TY; i += 2) {
             read_b(px, i + 1, b1);
@@ -311,7 +317,7 @@ __global__ __launch_bounds__(64 * (T3_NMW + T3_NLW), 1) void convtr_s3_kernel(co
 #endif
 #pragma unroll
             for (int q6 = 0; q6 < 6; ++q6)
-              acc[px][i >> 1][i & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[PA[q6]], b0[PB[q6]], acc[px][i >> 1][i & 1], 0, 0, 0);
+              acc[px][i >> 1][i & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[T3_PA[q6]], b0[T3_PB[q6]], acc[px][i >> 1][i & 1], 0, 0, 0);
             if (i + 2 < 2 * T3_TY) read_b(px, i + 2, b0);
             __builtin_amdgcn_sched_barrier(0);
 #ifdef FS_ABLATION
@@ -319,7 +325,7 @@ __global__ __launch_bounds__(64 * (T3_NMW + T3_NLW), 1) void convtr_s3_kernel(co
 #endif
 #pragma unroll
             for (int q6 = 0; q6 < 6; ++q6)
-              acc[px][(i + 1) >> 1][(i + 1) & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[PA[q6]], b1[PB[q6]], acc[px][(i + 1) >> 1][(i + 1) & 1], 0, 0, 0);
+              acc[px][(i + 1) >> 1][(i + 1) & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[T3_PA[q6]], b1[T3_PB[q6]], acc[px][(i + 1) >> 1][(i + 1) & 1], 0, 0, 0);
           }
         }
       }
@@ -439,13 +445,12 @@ __global__ __launch_bounds__(64 * (T3_NMW + T3_NLW), 1) void convtr_s3_kernel(co
 #ifdef FS_ABLATION
           if (p.ab & 128) continue;
 #endif
-          // the six products, small terms first: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
-          constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+          // the six products, small terms first (T3_PA / T3_PB)
 #pragma unroll
           for (int q = 0; q < 6; ++q)
 #pragma unroll
             for (int px = 0; px < 2; ++px)
-              acc[px][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[px][PA[q]], bq[px][PB[q]], acc[px][y], 0, 0, 0);
+              acc[px][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[px][T3_PA[q]], bq[px][T3_PB[q]], acc[px][y], 0, 0, 0);
         }
       }
     }

@@ -11,7 +11,9 @@
 //   FS_WPREP_TR32 p = {Cin, Cout, CinP, CoutT}              Wt[ci][tap 0..63][co 0..31] <- W[ci][co][tap]
 //       (`w` may point at a 32-channel slice of a [Cin][CoutT][64] tensor)            (convtr.hip)
 //   FS_WPREP_TR16 p = {Cin, Cout, CinP}                     Wt[ci][tap][co 0..15]
-//   FS_WPREP_P8   p = {Cin, Cout, CinP, RT}                 W'[ci][neighbour][row] (+16 pad) of the all-parities kernel
+//   FS_WPREP_P8   p = {Cin, Cout, CinP, RT, split}          W'[ci][neighbour][row] (+16 pad) of the all-parities kernel;
+//       split = 1 (CinP <= 32, RT <= 3): the same table as three bf16 pieces, words [chunk of 4 channels][row tile][piece 3]
+//       [(dz, dy) 4][row 16][x neighbour 2, the lower position first][channel pair] -- 1 KB per (chunk, row tile, piece)
 //   FS_WPREP_WINO p = {Cout, Cin, CinP, mode}              Ut[ci][kz*3+ky][t 0..3][co 0..63] (+16 pad per ci): the F(2,3)
 //       filter transform along kx of the taps FS_WPREP_FWD would deliver (same two modes)          (convwino.hpp)
 //   FS_WPREP_WINO4 p = {Cout, Cin, CinP, mode}             Ut[ci][kz*3+ky][t 0..5][co 0..63]: the F(4,3) filter transform
@@ -28,7 +30,7 @@ enum { FS_WPREP_FWD = 0, FS_WPREP_TR32 = 1, FS_WPREP_TR16 = 2, FS_WPREP_P8 = 3, 
        FS_WPREP_WINO2D = 6, FS_WPREP_S3K4 = 7, FS_WPREP_TRS3 = 8, FS_WPREP_TRS3_16 = 9 };
 
 // two floats -> one word of two bf16 (round to nearest even; low half = the first)
-__device__ __forceinline__ unsigned s3_pack(float a, float b) {
+__host__ __device__ __forceinline__ unsigned s3_pack(float a, float b) {
   typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
   const bf16x2_t h = {(__bf16)a, (__bf16)b};
   return __builtin_bit_cast(unsigned, h);
@@ -96,6 +98,33 @@ __device__ __forceinline__ unsigned wprep_t3_word16(const FsWprepJob& j, int e) 
   for (int i = 0; i < 2; ++i) {
     const int ci = 4 * st + 2 * c2 + i;
     float a = (co < Cout && ci < Cin) ? w[((size_t)ci * CoutT + co) * 64 + tap] : 0.f;
+    for (int q = 0; q < piece; ++q) a = a - (float)(__bf16)a;  // exact
+    v[i] = a;
+  }
+  return s3_pack(v[0], v[1]);
+}
+// one word of the split FS_WPREP_P8 table (round 13; the all-parities kernel on split-bf16 MFMAs, <= 32 input channels and
+// <= 3 row tiles).  Word index: ((((chunk RT + row tile) 3 + piece) 4 + kq) 16 + row) 4 + x slot 2 + channel pair: bf16 piece
+// `piece` of channels (2 cp, 2 cp + 1) of the chunk's four, for neighbour (dz, dy) = (kq >> 1, kq & 1), dx = 1 - x slot (the
+// lower input position q - 1 first, as the piece image orders them) and row = px 8 + item % 8 of the row tile, item =
+// (pz 2 + py) Cout + co.  Zero for items >= 4 Cout and channels >= Cin.  (__host__ as well: the layout is checked on the
+// CPU, tests/test_tr_p8_s3_build.py)
+__host__ __device__ __forceinline__ unsigned wprep_p8s_word(const FsWprepJob& j, int e) {
+  const int Cin = j.p[0], Cout = j.p[1], RT = j.p[3];
+  const float* __restrict__ w = j.w;
+  const int cp = e & 1, xs = (e >> 1) & 1, row = (e >> 2) & 15, kq = (e >> 6) & 3;
+  int r = e >> 8;
+  const int piece = r % 3; r /= 3;
+  const int rt = r % RT, chunk = r / RT;
+  const int px = row >> 3, item = 8 * rt + (row & 7);
+  const bool iok = item < 4 * Cout;
+  const int pzy = iok ? item / Cout : 0, co = iok ? item - pzy * Cout : 0;
+  const int kz = wprep_p8_k(pzy >> 1, kq >> 1), ky = wprep_p8_k(pzy & 1, kq & 1), kx = wprep_p8_k(px, 1 - xs);
+  float v[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int ci = 4 * chunk + 2 * cp + i;
+    float a = (iok && ci < Cin) ? w[((size_t)ci * Cout + co) * 64 + (kz * 4 + ky) * 4 + kx] : 0.f;
     for (int q = 0; q < piece; ++q) a = a - (float)(__bf16)a;  // exact
     v[i] = a;
   }
@@ -186,6 +215,7 @@ __device__ __forceinline__ float wprep_elem(const FsWprepJob& j, int e) {
     }
     default: {  // FS_WPREP_P8
       const int Cin = j.p[0], Cout = j.p[1], RT = j.p[3];
+      if (j.p[4] != 0) return __builtin_bit_cast(float, wprep_p8s_word(j, e));  // the split table's words
       const int wsci = 128 * RT + 16;
       const int ci = e / wsci, i = e - ci * wsci;
       if (i >= 128 * RT || ci >= Cin) return 0.f;

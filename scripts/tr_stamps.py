@@ -1,11 +1,13 @@
 """Where one brick of the parities-in-rows heads kernel (convtr_p8_kernel) spends its cycles: s_memtime stamps of
-the matrix waves (library built with -DFS_TR_STAMPS; csrc/convtr.hip).  GPU box only."""
+the matrix waves (library built with -DFS_TR_STAMPS; csrc/convtr.hip).  GPU box only.  `tr_stamps.py [COUT]`: 6 = the flow
+head (default), 1 = the mask head."""
 import os, sys, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from opticalflowscivis_amd import ops, _lib
+cout = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 x = torch.randn(2, 32, 128, 128, 128, device="cuda")
-w = torch.randn(32, 6, 4, 4, 4, device="cuda") * 0.05
+w = torch.randn(32, cout, 4, 4, 4, device="cuda") * 0.05
 for _ in range(3):
     ops.conv3d_tr(x, w, None)
 torch.cuda.synchronize()
