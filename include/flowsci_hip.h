@@ -59,8 +59,10 @@ enum {
  *        fs_region_follow2d / fs_region_follow3d (connected regions of flag maps, their table, where the flow carries them).
  *   440  fs_raycast3d / fs_raycast3d_ws_bytes, fs_brick_range3d (volumes to images: emission / absorption and maximum
  *        intensity through a transfer function, with per-brick value ranges to jump over empty space).
- *   450  fs_iso_count3d / fs_iso_emit3d / fs_iso3d_ws_bytes (volumes to indexed triangle meshes: marching tetrahedra). */
-#define FS_ABI_VERSION 450
+ *   450  fs_iso_count3d / fs_iso_emit3d / fs_iso3d_ws_bytes (volumes to indexed triangle meshes: marching tetrahedra).
+ *   460  fs_lic2d / fs_lic3d and their _ws_bytes queries (line integral convolution: a texture averaged along the
+ *        streamlines of step flows). */
+#define FS_ABI_VERSION 460
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -1114,6 +1116,53 @@ int fs_iso_count3d(const float* volumes, int K, int D, int H, int W, long long s
 int fs_iso_emit3d(const float* volumes, int K, int D, int H, int W, long long sstride, double iso, const double* spacing,
                   const unsigned char* ws, const long long* row_offsets, long long V, long long T, const float* values,
                   int F, float* vertices, float* normals, float* values_out, int* faces, int* status, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Line integral convolution -- every node's value is a texture averaged along the streamline of the normalised field
+ * through that node, L steps of length h each way; K fields and both directions in one call (a streaming pre-pass that
+ * packs field and texture into 16-byte elements, then one launch for all the lines).
+ *   flows: as for fs_advect*: K fields of C fp32 planes of D*H*W elements (2-D: D = 1, C = 2; 3-D: C = 3), field k at
+ *     + k * flow_sstride elements (flow_sstride >= C*D*H*W when K > 1); channel 0 along W.  Each field is steady.
+ *   tex: one fp32 plane of D*H*W elements per step, step k at + k * tex_sstride (>= D*H*W when K > 1), or
+ *     tex_sstride = 0: one texture shared by all K steps.
+ *   weights: fp64 [L+1] in DEVICE memory: w[0] for the node, w[i] for the i-th sample on either side.  Precondition (the
+ *     library cannot read them): all finite, w[0] > 0, the others >= 0.
+ *   L: 0 .. FS_LIC_MAX_L steps each way.  h: the step length in elements, finite and > 0.  vmin: finite and >= 0.
+ *   method: FS_ADV_EULER or FS_ADV_RK2 (midpoint).
+ *   out: fp32 [K][D*H*W], contiguous.  ends: uint8 [K][D*H*W] or NULL.  count: int32 [K][D*H*W] or NULL.
+ *   ws: fs_lic{2,3}d_ws_bytes(K, ...) bytes (16 per node and step), 16-byte aligned: the packed image (v_x, v_y[, v_z],
+ *     tex) the lines are sampled from, written by the call before it is read.  It holds nothing afterwards.
+ *   Per node, in fp64 without fused multiply-adds; square root and division are correctly rounded (nothing is
+ *   multiplied by a reciprocal); positions stay fp64 for the whole line (a restatement with the same operations in the
+ *   same order reproduces every output bit, end code and count):
+ *     sample(k, q), classify(p): those of fs_advect* above, the clamp included.
+ *     dir(k, q): v = sample(k, q).  Any v_c not finite: NONFINITE.  n2 = (v0*v0 + v1*v1) + v2*v2 (2-D: no third term),
+ *       n = sqrt(n2).  !(n > vmin): STAGNANT.  Else d_c = v_c / n.
+ *     tsample(k, q): sample's clamp, corner and weight rule on the step's one texture plane, every product formed (a
+ *       non-finite texture value propagates, also through a weight of 0).
+ *     One side, for s = +1 and then s = -1, with hs = s * h and hh = 0.5 * hs formed on the host: p = the node's integer
+ *       coordinates, A = 0.0, Wt = 0.0, n = 0, end = FULL.  For i = 1 .. L:
+ *         d = dir(k, p); a code ends the side with that code.  RK2 only: d = dir(k, p + hh * d); likewise.
+ *         p' = p + hs * d.  classify(p') not ALIVE: the side ends with OUT; the exit point is not sampled.
+ *         Else p = p', A = A + w[i] * tsample(k, p), Wt = Wt + w[i], n += 1.
+ *     acc = (w[0] * tsample(k, node) + A_fwd) + A_bwd;  wsum = (w[0] + Wt_fwd) + Wt_bwd;  out = (float)(acc / wsum);
+ *     ends = end_fwd | end_bwd << 2;  count = 1 + n_fwd + n_bwd.
+ *   Every index is formed from a finite value clamped to the grid: no input makes the kernel read outside its operands.
+ *   FS_ERR_NULLPTR: flows, tex, weights, out or ws NULL.  FS_ERR_SHAPE: K < 1, C other than 2 (2-D) / 3 (3-D), an extent
+ *   < 1, a stride below its minimum.  FS_ERR_ARG: L outside 0 .. FS_LIC_MAX_L, h not finite or <= 0, vmin not finite or
+ *   < 0, a method other than the two, ws not 16-byte aligned.  All of them are returned before anything is launched; the
+ *   _ws_bytes queries launch nothing and return the byte count or -(FS_ERR_*).
+ */
+#define FS_LIC_MAX_L 1024
+enum { FS_LIC_FULL = 0, FS_LIC_OUT = 1, FS_LIC_STAGNANT = 2, FS_LIC_NONFINITE = 3 };
+long long fs_lic2d_ws_bytes(int K, int H, int W);
+long long fs_lic3d_ws_bytes(int K, int D, int H, int W);
+int fs_lic2d(const float* flows, int K, int C, int H, int W, long long flow_sstride, const float* tex,
+             long long tex_sstride, const double* weights, int L, double h, double vmin, int method, float* out,
+             unsigned char* ends, int* count, void* ws, fs_stream_t stream);
+int fs_lic3d(const float* flows, int K, int C, int D, int H, int W, long long flow_sstride, const float* tex,
+             long long tex_sstride, const double* weights, int L, double h, double vmin, int method, float* out,
+             unsigned char* ends, int* count, void* ws, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

@@ -3702,6 +3702,148 @@ def isosurface_check(result):
 
 
 # --------------------------------------------------------------------------------------------
+# Line integral convolution: a texture averaged along the streamlines of step flows (fs_lic{2,3}d)
+# --------------------------------------------------------------------------------------------
+LIC_FULL, LIC_OUT, LIC_STAGNANT, LIC_NONFINITE = 0, 1, 2, 3  # FS_LIC_*: how a side of a line ended
+LIC_MAX_L = 1024  # FS_LIC_MAX_L
+_LIC_METHODS = {"euler": (0, 1), "rk2": (1, 2)}  # name -> (FS_ADV_*, field samples per step)
+_LIC_KERNELS = ("box", "hann")
+
+
+def _lic_length(L):
+    if isinstance(L, bool) or int(L) != L or not (0 <= int(L) <= LIC_MAX_L):
+        raise ValueError("length must be an integer in 0..%d, got %r" % (LIC_MAX_L, L))
+    return int(L)
+
+
+def lic_weights(L, kernel="box", device="cuda"):
+    """fp64 [L+1] weights of ops.lic on `device`: w[0] for the node, w[i] for the i-th sample on either side.  "box":
+    all 1; "hann": 0.5 * (1 + cos(pi * i / (L + 1))), computed on the host in fp64."""
+    import math
+    L = _lic_length(L)
+    if kernel == "box":
+        w = [1.0] * (L + 1)
+    elif kernel == "hann":
+        w = [0.5 * (1.0 + math.cos(math.pi * i / (L + 1))) for i in range(L + 1)]
+    else:
+        raise ValueError("kernel must be one of %s, got %r" % (list(_LIC_KERNELS), kernel))
+    return torch.tensor(w, dtype=torch.float64).to(device)
+
+
+def lic_noise(shape, seed=0, device="cuda"):
+    """fp32 white noise, uniform in [0,1), of spatial `shape`: drawn by a CPU generator seeded with `seed` and copied
+    to `device`, so a seed names the same texture on every device."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) < 1 or min(shape) < 1:
+        raise ValueError("shape must have every extent >= 1, got %r" % (shape,))
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    return torch.rand(shape, generator=g, dtype=torch.float32).to(device)
+
+
+def lic_cost(shape, K, L, method="rk2", with_ends=True, with_count=True, shared_tex=False):
+    """(HBM bytes, flops) the algorithm needs for one lic call on K fields of spatial `shape` with L steps each way,
+    every line at full length (lines that leave the grid or stagnate do less): the fields and the textures read once,
+    out / ends / count written once, the weights read once (the packed image the kernel samples from, 16 bytes per
+    node written and read again, is the implementation's and not counted).  Flops per field sample as in advect_cost (2^C corner
+    weights of C - 1 products, 2 per corner and plane, ~4 C for clamp / floor / fractions), plus 2 C for n2 and its root
+    and C divisions, 2 C for the point it is taken at; per texture sample the same with one plane, plus 3 for the two
+    sums and ~2 C for the classification; 5 for the node's quotient."""
+    if method not in _LIC_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(_LIC_METHODS), method))
+    L = _lic_length(L)
+    shape = tuple(int(s) for s in shape)
+    C = len(shape)
+    if C not in (2, 3) or min(shape) < 1:
+        raise ValueError("shape must be (H,W) or (D,H,W) with every extent >= 1, got %r" % (shape,))
+    K = int(K)
+    plane = 1
+    for s in shape:
+        plane *= s
+    nbytes = 4 * K * C * plane + 4 * (1 if shared_tex else K) * plane + 4 * K * plane + 8 * (L + 1)
+    nbytes += (K * plane if with_ends else 0) + (4 * K * plane if with_count else 0)
+    corners = 1 << C
+    vsample = corners * (C - 1) + 2 * corners * C + 4 * C + 3 * C + 2 * C
+    tsample = corners * (C - 1) + 2 * corners + 4 * C + 3 + 2 * C
+    per_node = 2 * L * _LIC_METHODS[method][1] * vsample + (2 * L + 1) * tsample + 5
+    return nbytes, K * plane * per_node
+
+
+def lic(flows, tex, length=16, h=0.5, method="rk2", kernel="box", vmin=0.0, with_ends=True, with_count=True):
+    """Line integral convolution of K steady fields in one launch (fs_lic{2,3}d): every node's value is `tex` averaged
+    along the streamline of the normalised field through that node, `length` steps of `h` elements each way.
+
+    flows: [K,2,H,W] or [K,3,D,H,W] fp32 on a GPU (channel 0 along W); the step stride may be anything (flows[::2]
+    passes as it is).  tex: [*sp] (one texture for every step) or [K,*sp] (a pass's output fed back).  method: "euler"
+    or "rk2" (midpoint) on the unit direction field.  kernel: "box", "hann" or an fp64-convertible weight tensor
+    [length+1] (w[0] the node's, w[i] the i-th sample's on either side), which is validated on the host -- all finite,
+    w[0] > 0, the others >= 0 -- with ONE synchronisation when it lives on a device; the named kernels never
+    synchronise.  vmin: a side ends STAGNANT where the speed is not above vmin (0: only where it is exactly 0).
+
+    All arithmetic is fp64 (include/flowsci_hip.h states the order of operations; tests/lic_ref.py restates it and
+    agrees bit for bit).  A side also ends where the next point would leave the grid (OUT: the border is inside, the
+    exit point is not sampled) or the field is not finite (NONFINITE); a non-finite texture value propagates.
+
+    Returns a dict: out fp32 [K,*sp]; ends uint8 [K,*sp] (LIC_* of the forward side | the backward side's << 2) or
+    None; count int32 [K,*sp] (the samples averaged, the node's included) or None.  The call allocates the kernel's
+    workspace, 16 bytes per node and step, for its own duration.  A measurement on detached values: nothing is
+    differentiated."""
+    if method not in _LIC_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(_LIC_METHODS), method))
+    L = _lic_length(length)
+    h, vmin = float(h), float(vmin)
+    if not (0.0 < h < float("inf")):
+        raise ValueError("h must be finite and > 0, got %r" % (h,))
+    if not (0.0 <= vmin < float("inf")):
+        raise ValueError("vmin must be finite and >= 0, got %r" % (vmin,))
+    flows, nd = _advect_flows(flows)
+    dev = flows.device
+    K = int(flows.shape[0])
+    sp = tuple(int(s) for s in flows.shape[2:])
+    if not isinstance(tex, torch.Tensor):
+        raise ValueError("tex must be a tensor")
+    if not tex.is_cuda:
+        raise ValueError("tex must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (tex.device,))
+    if tex.device != dev:
+        raise ValueError("tex must be on the flows' device %s, got %s" % (dev, tex.device))
+    if tuple(tex.shape) not in (sp, (K,) + sp):
+        raise ValueError("tex must be %s or %s, got %s" % (sp, (K,) + sp, tuple(tex.shape)))
+    tex = tex.detach()
+    if tex.dtype != torch.float32:
+        tex = tex.to(torch.float32)
+    tex = tex.contiguous()
+    plane = 1
+    for v in sp:
+        plane *= v
+    shared = tex.dim() == nd
+    if isinstance(kernel, str):
+        w = lic_weights(L, kernel, dev)
+    else:
+        w = torch.as_tensor(kernel).detach().to(torch.float64).reshape(-1)
+        if w.numel() != L + 1:
+            raise ValueError("a weight tensor must hold length + 1 = %d values, got %d" % (L + 1, w.numel()))
+        wh = w.cpu()  # the one synchronisation
+        if not bool(torch.isfinite(wh).all()) or not float(wh[0]) > 0.0 or bool((wh[1:] < 0).any()):
+            raise ValueError("weights must be finite with w[0] > 0 and the others >= 0")
+        w = w.to(dev).contiguous()
+    out = torch.empty((K,) + sp, dtype=torch.float32, device=dev)
+    ends = torch.empty((K,) + sp, dtype=torch.uint8, device=dev) if with_ends else None
+    count = torch.empty((K,) + sp, dtype=torch.int32, device=dev) if with_count else None
+    fss = flows.stride(0) if K > 1 else nd * plane  # (a single field's step stride is never used)
+    nbytes, flops = lic_cost(sp, K, L, method, with_ends, with_count, shared)
+    wsb = getattr(_lib.lib(), "fs_lic%dd_ws_bytes" % nd)(K, *sp)
+    if wsb < 0:
+        _lib.check(int(-wsb), "fs_lic%dd_ws_bytes" % nd)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)  # the packed (field, texture) image: 16 bytes per node and step
+    args = (flows.data_ptr(), K, nd) + sp + (fss, tex.data_ptr(), 0 if shared else plane, w.data_ptr(), L, h, vmin,
+                                             _LIC_METHODS[method][0], out.data_ptr(), _ptr(ends), _ptr(count),
+                                             ws.data_ptr(), _stream(flows))
+    with torch.cuda.device(dev):
+        _call("fs_lic%dd" % nd, *args, algo_bytes=nbytes, algo_flops=flops)
+    return {"out": out, "ends": ends, "count": count}
+
+
+# --------------------------------------------------------------------------------------------
 # Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
 # --------------------------------------------------------------------------------------------
 import numpy as _np
