@@ -722,6 +722,19 @@ int fs_flow_metrics3d(const float* pred, const float* gt, int N, int C, int D, i
                       float tau_abs, float tau_rel, float* epe_map, double* ws, double* out, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The fp64 sample of a step flow -- the one rule by which fs_flow_consistency*, fs_advect* and fs_lic* read a field (or
+ * an image or texture plane) at a point and decide whether a point is on the grid (csrc/trilinear64.hpp).  S = (W, H, D)
+ * nodes per axis (2-D: D = 1), points of C components (x, y[, z]) in elements; fp64 without fused multiply-adds:
+ *   classify(p): any p_c not finite: non-finite.  Else p_c < 0 or p_c > S_c - 1 for some c: outside (the border is
+ *     inclusive; an extent of 1 is legal).  Else on the grid.
+ *   sample(q): any q_c not finite -> every value NaN (no index is formed).  Else q_c = min(max(q_c, 0), S_c - 1) (nothing
+ *     to do for a point that classify found on the grid), i0 = floor(q_c), f_c = q_c - i0, g_c = 1 - f_c,
+ *     i1 = min(i0 + 1, S_c - 1); the corner with bits (bz, by, bx) weighs (tz * ty) * tx (2-D: ty * tx), t = f where the
+ *     bit is set, else g; the sum over the corners in ascending 4 bz + 2 by + bx, from 0.0, of weight * plane[corner],
+ *     every product formed (a non-finite corner of weight 0 gives NaN).
+ */
+
+/* ------------------------------------------------------------------------------------
  * Forward-backward consistency -- the label-free quality measure of a flow: N pairs of displacements, one launch.
  *   flow_f, flow_b: N flows of C fp32 planes of D*H*W (2-D: D = 1, C = 2; 3-D: C = 3) elements each, laid out and
  *     strided exactly as fs_flow_metrics*'s operands (planes of one flow contiguous, flow n at + n * bstride elements,
@@ -731,13 +744,10 @@ int fs_flow_metrics3d(const float* pred, const float* gt, int N, int C, int D, i
  *   valid: uint8 [N, D, H, W] (contiguous, nonzero = set) or NULL = every element is valid.
  *   Per element x, in fp64 without fused multiply-adds (a restatement with the same operations in the same order
  *   reproduces every count exactly):
- *     p_c = x_c + flow_f_c(x).  A non-finite flow_f_c(x): NONFINITE.  Else p_c < 0 or p_c > S_c - 1 for some c:
- *     OUTGOING (the border is inclusive; an extent of 1 is legal).  Else i0 = floor(p_c), f_c = p_c - i0,
- *     g_c = 1 - f_c, i1 = min(i0 + 1, S_c - 1); the corner with bits (bz, by, bx) weighs (tz * ty) * tx (2-D: ty * tx),
- *     t = f where the bit is set, else g; Fbw_c = the sum over the corners in ascending 4 bz + 2 by + bx, from 0.0, of
- *     weight * flow_b_c[corner], every product formed (a non-finite corner of weight 0 gives NaN); I1w likewise from
- *     img1.  r2 = sum_c (flow_f_c + Fbw_c)^2, m2 = sum_c flow_f_c^2 + sum_c Fbw_c^2 (each sum in ascending c from
- *     0.0), r = sqrt(r2), e = I1w - img0(x).  Fbw, or with images img0(x) or I1w, not finite: NONFINITE.  Else
+ *     p_c = x_c + flow_f_c(x).  A non-finite flow_f_c(x): NONFINITE.  Else classify(p) outside: OUTGOING.  Else
+ *     Fbw_c = sample(p) of flow_b_c and I1w = sample(p) of img1 ("The fp64 sample of a step flow" above).
+ *     r2 = sum_c (flow_f_c + Fbw_c)^2, m2 = sum_c flow_f_c^2 + sum_c Fbw_c^2 (each sum in ascending c from 0.0),
+ *     r = sqrt(r2), e = I1w - img0(x).  Fbw, or with images img0(x) or I1w, not finite: NONFINITE.  Else
  *     OCCLUDED when r2 > alpha1 * m2 + alpha2 (UnFlow: 0.01, 0.5), CONSISTENT otherwise.  inside = OCCLUDED + CONSISTENT.
  *   out: fp64 [N][FS_FLOW_CONSISTENCY_K], over the elements with `valid` set:
  *     0 n_valid   1 n_nonfinite   2 n_outgoing   3 n_occluded   4 n_consistent
@@ -782,13 +792,8 @@ int fs_flow_consistency3d(const float* flow_f, const float* flow_b, int N, int C
  *     are formed on the host in fp64 (scale = -1 with the opposite flows traces backward in time).
  *   Per particle, in fp64 without fused multiply-adds (a restatement with the same operations in the same order
  *   reproduces every output bit, status and count):
- *     sample(k, q): any q_c not finite -> every component NaN (no index is formed).  Else q_c = min(max(q_c, 0), S_c - 1),
- *       i0 = floor(q_c), f_c = q_c - i0, g_c = 1 - f_c, i1 = min(i0 + 1, S_c - 1); the corner with bits (bz, by, bx) weighs
- *       (tz * ty) * tx (2-D: ty * tx), t = f where the bit is set, else g; the sum over the corners in ascending
- *       4 bz + 2 by + bx, from 0.0, of weight * flows_k,c[corner], every product formed (a non-finite corner of weight 0
- *       gives NaN).
- *     classify(p): any p_c not finite: NONFINITE.  Else p_c < 0 or p_c > S_c - 1 for some c: OUT (the border is inside).
- *       Else ALIVE.
+ *     sample(k, q): the sample of "The fp64 sample of a step flow" above on the C planes of field k, the clamp included.
+ *     classify(p): that section's: non-finite is NONFINITE, outside is OUT (the border is inside), on the grid is ALIVE.
  *     Step k: the fp32 position (pos_in at k = 0, the previous step's result later) is widened; an ALIVE particle is
  *       classified (a seed outside the box or a non-finite seed ends here without moving).  For s in 0..S-1 while ALIVE,
  *       with k1 = sample(k, p): Euler p' = p + hs k1; RK2 k2 = sample(p + (0.5 hs) k1), p' = p + hs k2; RK4 the classical
@@ -1135,7 +1140,7 @@ int fs_iso_emit3d(const float* volumes, int K, int D, int H, int W, long long ss
  *   Per node, in fp64 without fused multiply-adds; square root and division are correctly rounded (nothing is
  *   multiplied by a reciprocal); positions stay fp64 for the whole line (a restatement with the same operations in the
  *   same order reproduces every output bit, end code and count):
- *     sample(k, q), classify(p): those of fs_advect* above, the clamp included.
+ *     sample(k, q), classify(p): those of fs_advect* ("The fp64 sample of a step flow" above), the clamp included.
  *     dir(k, q): v = sample(k, q).  Any v_c not finite: NONFINITE.  n2 = (v0*v0 + v1*v1) + v2*v2 (2-D: no third term),
  *       n = sqrt(n2).  !(n > vmin): STAGNANT.  Else d_c = v_c / n.
  *     tsample(k, q): sample's clamp, corner and weight rule on the step's one texture plane, every product formed (a

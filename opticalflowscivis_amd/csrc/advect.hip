@@ -4,11 +4,11 @@
 //
 // Per particle (fp64, contraction off: a numpy fp64 restatement with the same operations in the same order reproduces
 // every position bit, every status and every count -- tests/advect_ref.py):
-//   sample(k, q): a non-finite q_c -> every component NaN, no index formed; else q_c = min(max(q_c, 0), S_c - 1), then
-//     flowconsist.hip's rule: i0 = floor(q_c), f = q_c - i0, g = 1 - f, i1 = min(i0 + 1, S_c - 1); corner (bz, by, bx)
-//     weighs (tz ty) tx, t = f where the bit is set, else g; the sum over corners in ascending 4 bz + 2 by + bx of
-//     w * value, from 0.0, ALL products formed (a non-finite corner of weight 0 gives NaN)
-//   classify(p): a non-finite p_c -> NONFINITE; else p_c < 0 or p_c > S_c - 1 -> OUT (border inclusive); else ALIVE
+//   sample(k, q) and classify(p): the rule trilinear64.hpp states (a non-finite q samples NaN with no index formed, any
+//     other q is clamped to the grid; p is NONFINITE, OUT (border inclusive) or ALIVE).  They are their OWN copy of
+//     those lines and do not include the header: on it the 3-D Euler kernel measured 0.9 % slower on 10^4 scattered
+//     seeds in three sessions, outside the parent's spread (profiles/trilinear64.txt) -- a change to the rule is made
+//     there and here
 //   step k: the fp32 position (pos_in, later the previous step's result) is widened; an ALIVE particle is classified
 //     (a seed outside the box or a NaN seed ends here without moving); while ALIVE, each substep forms p' (stage points
 //     are clamped by sample, never classified) and classifies it: NONFINITE keeps p, OUT and ALIVE take p'; `steps`

@@ -99,6 +99,28 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// the fp64 wave butterflies of the measurement kernels' first reduction stage
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// host-side argument check: a spacing, scale or step that is positive and finite
+inline bool pos_finite(double v) { return v > 0.0 && v < HUGE_VAL; }
+
 // Second stage of the deterministic reductions: `nblocks` pairs of per-block partial sums in
 // `ws` -> sums[0..1].  One block, fixed order, fp64 accumulation: bitwise reproducible.
 static __global__ __launch_bounds__(256) void reduce_final_kernel(const float* __restrict__ ws, int nblocks,

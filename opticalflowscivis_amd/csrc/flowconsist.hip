@@ -8,9 +8,10 @@
 // Per element x (fp64, contraction off: a numpy fp64 restatement with the same operations in the same order reproduces
 // every count exactly -- tests/flow_consistency_ref.py):
 //   p_c = x_c + F_f,c(x); a non-finite F_f,c -> NONFINITE; else p_c < 0 or p_c > S_c - 1 -> OUTGOING (border inclusive)
-//   i0 = floor(p_c), f = p_c - i0, g = 1 - f, i1 = min(i0 + 1, S_c - 1); corner (bz, by, bx) weighs (tz ty) tx, t = f
-//   where the bit is set, else g; Fbw_c and I1w = sum over corners in ascending 4 bz + 2 by + bx of w * value, from 0.0,
-//   ALL products formed (a non-finite corner of weight 0 gives NaN: it lies inside the support's closure)
+//   Fbw_c and I1w = flow_b's C planes and img1 sampled at p by the rule trilinear64.hpp states (p lies inside: nothing
+//   to clamp).  element() keeps its OWN copy of those lines and does not include the header: on corners64 the 3-D
+//   kernels measured 2 - 3 % slower on white-noise flows, outside the parent's spread, with equal instruction counts
+//   (profiles/trilinear64.txt) -- a change to the rule is made there and here
 //   r2 = sum_c (F_f,c + Fbw_c)^2, m2 = sum_c F_f,c^2 + sum_c Fbw_c^2, r = sqrt(r2), e = I1w - I0(x)
 //   Fbw (or, with images, I0(x) or I1w) not finite -> NONFINITE; else r2 > alpha1 m2 + alpha2 -> OCCLUDED, else CONSISTENT
 //
@@ -142,18 +143,6 @@ __device__ __forceinline__ int element(const float (&ff)[3], float i0v, int d, i
   return occ ? FS_FC_OCCLUDED : FS_FC_CONSISTENT;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // V: elements per thread and step (4 when the plane size is a multiple of 4, else 1); VEC: they move as one 16-byte
 // (maps and mask: 4-byte) access, which needs aligned pointers and strides.  Which elements a thread takes depends on V
 // only, so a misaligned copy of the same operands gives the same sums bit for bit.
@@ -263,7 +252,7 @@ __global__ __launch_bounds__(NT) void flow_consistency_kernel(const float* __res
   double v[K] = {(double)a.n, (double)a.nnf, (double)a.nout, (double)a.nocc, (double)a.nnoc, a.sr, a.sr2, a.mx,
                  a.srn, a.sa, a.se2, a.san, a.se2n};
 #pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = (k == FS_FC_MAX_R) ? wave_max(v[k]) : wave_sum(v[k]);
+  for (int k = 0; k < K; ++k) v[k] = (k == FS_FC_MAX_R) ? fs::wave_max(v[k]) : fs::wave_sum(v[k]);
   __shared__ double red[NT / 64][K];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) {

@@ -91,18 +91,6 @@ __device__ __forceinline__ void element(const float (&p)[3], const float (&g)[3]
   if (nc) { a.sen += epe; a.se2n += e2; a.saen += ae; }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 template <int C, int V, bool RIFE>
 __global__ __launch_bounds__(NT) void flow_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                           const unsigned char* __restrict__ valid,
@@ -184,7 +172,7 @@ __global__ __launch_bounds__(NT) void flow_metrics_kernel(const float* __restric
   double v[K] = {(double)a.n, a.se, a.se2, a.sae, (double)a.nout, a.mx,
                  (double)a.nn, a.sen, a.se2n, a.saen, (double)a.nnout, (double)a.nf, (double)a.nfn};
 #pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = (k == FS_FM_MAX_EPE) ? wave_max(v[k]) : wave_sum(v[k]);
+  for (int k = 0; k < K; ++k) v[k] = (k == FS_FM_MAX_EPE) ? fs::wave_max(v[k]) : fs::wave_sum(v[k]);
   __shared__ double red[NT / 64][K];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) {

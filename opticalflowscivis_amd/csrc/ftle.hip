@@ -118,24 +118,6 @@ __device__ __forceinline__ int node(const float* __restrict__ map, const unsigne
   return isfinite(res) ? FS_FTLE_OK : FS_FTLE_NONFINITE;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 template <int C>
 __global__ __launch_bounds__(NT) void ftle_kernel(const float* __restrict__ map,
                                                   const unsigned char* __restrict__ status,
@@ -174,7 +156,8 @@ __global__ __launch_bounds__(NT) void ftle_kernel(const float* __restrict__ map,
   // workgroup reduction: wave butterflies, then the four waves in a fixed order
   double v[K] = {(double)cnt[0], (double)cnt[1], (double)cnt[2], (double)cnt[3], (double)cnt[4], s1, s2, mn, mx};
 #pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = k == FS_FTLE_MIN ? wave_min(v[k]) : k == FS_FTLE_MAX ? wave_max(v[k]) : wave_sum(v[k]);
+  for (int k = 0; k < K; ++k)
+    v[k] = k == FS_FTLE_MIN ? fs::wave_min(v[k]) : k == FS_FTLE_MAX ? fs::wave_max(v[k]) : fs::wave_sum(v[k]);
   __shared__ double red[NT / 64][K];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) {
@@ -224,8 +207,6 @@ int plan(bool is3d, int C, int Gd, int Gh, int Gw, FP& f) {
   return FS_OK;
 }
 
-inline bool pos_finite(double v) { return v > 0.0 && v < HUGE_VAL; }
-
 int launch(bool is3d, const float* map, long long mcs, const unsigned char* status, const unsigned char* valid, int C,
            int Gd, int Gh, int Gw, const double* inv_h, const double* inv_2h, double inv_T, int accept_out,
            float* ftle, unsigned char* cls, float* cg, double* ws, double* out, fs_stream_t stream) {
@@ -237,11 +218,11 @@ int launch(bool is3d, const float* map, long long mcs, const unsigned char* stat
   const int rc = plan(is3d, C, Gd, Gh, Gw, f);
   if (rc != FS_OK) return rc;
   if (mcs < (long long)f.P) return FS_ERR_SHAPE;
-  if (!pos_finite(inv_T)) return FS_ERR_ARG;
+  if (!fs::pos_finite(inv_T)) return FS_ERR_ARG;
   for (int c = 0; c < 3; ++c) {
     f.ih[c] = c < C ? inv_h[c] : 0.0;
     f.i2h[c] = c < C ? inv_2h[c] : 0.0;
-    if (c < C && !(pos_finite(f.ih[c]) && pos_finite(f.i2h[c]))) return FS_ERR_ARG;
+    if (c < C && !(fs::pos_finite(f.ih[c]) && fs::pos_finite(f.i2h[c]))) return FS_ERR_ARG;
   }
   f.mcs = mcs; f.inv_T = inv_T; f.accept_out = accept_out != 0;
   const hipStream_t s = (hipStream_t)stream;

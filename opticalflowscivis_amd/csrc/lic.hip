@@ -4,7 +4,7 @@
 // Per node (fp64, contraction off, correctly rounded sqrt and division, positions fp64 for the whole line: a numpy fp64
 // restatement with the same operations in the same order reproduces every output bit, end code and count --
 // tests/lic_ref.py; include/flowsci_hip.h "Line integral convolution" states the rule):
-//   sample / classify: advect.hip's, restated here (the two files are merged once both are pinned bitwise)
+//   sample / classify: trilinear64.hpp's, the rule advect.hip restates (a non-finite q samples NaN, another is clamped)
 //   dir(k, q): v = sample(k, q); a non-finite v_c -> NONFINITE; n = sqrt((v0 v0 + v1 v1) + v2 v2); !(n > vmin) ->
 //     STAGNANT; d_c = v_c / n
 //   tsample(k, q): sample's clamp, corners and weights on the step's one texture plane
@@ -25,6 +25,7 @@
 // index is formed from a finite value clamped to the grid: no input makes the kernels read outside their operands, and
 // the pre-pass writes exactly the K * D*H*W elements the size query counts.
 #include "common.hpp"
+#include "trilinear64.hpp"
 
 namespace {
 
@@ -71,14 +72,7 @@ struct PackedSrc {
 
 template <int C>
 __device__ __forceinline__ bool alive(const double (&p)[3], const LP& a) {
-  const int S[3] = {a.W, a.H, a.D};
-  bool fin = true, out = false;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    fin = fin && isfinite(p[c]);
-    out = out || p[c] < 0.0 || p[c] > (double)(S[c] - 1);
-  }
-  return fin && !out;
+  return fs::finite_point<C>(p) && !fs::outside<C>(p, fs::Extent{a.W, a.H, a.D});
 }
 
 // v = the field (WV) and t = the texture (WT) sampled at q.  Every index comes from a finite value clamped to
@@ -86,45 +80,18 @@ __device__ __forceinline__ bool alive(const double (&p)[3], const LP& a) {
 template <int C, bool WV, bool WT, class Src>
 __device__ __forceinline__ void gather(const Src& src, const LP& a, const double (&q)[3], double (&v)[3], double& t) {
 #pragma clang fp contract(off)
-  bool fin = true;
-#pragma unroll
-  for (int c = 0; c < C; ++c) fin = fin && isfinite(q[c]);
-  if (!fin) {
+  if (!fs::finite_point<C>(q)) {
 #pragma unroll
     for (int c = 0; c < C; ++c) v[c] = __builtin_nan("");
     t = __builtin_nan("");
     return;
   }
-  const int S[3] = {a.W, a.H, a.D};
-  const size_t st[3] = {(size_t)1, (size_t)a.W, (size_t)a.W * (size_t)a.H};
-  double fr[3], gr[3];
-  size_t o0[3], o1[3];
+  const fs::Extent e{a.W, a.H, a.D};
+  double qc[3] = {0.0, 0.0, 0.0}, s[3] = {0.0, 0.0, 0.0}, ts = 0.0;
 #pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const double hi = (double)(S[c] - 1);
-    double qc = q[c] < 0.0 ? 0.0 : q[c];
-    qc = qc > hi ? hi : qc;
-    const double fl = floor(qc);
-    const int i0 = (int)fl;
-    const int i1 = i0 + 1 < S[c] ? i0 + 1 : S[c] - 1;
-    fr[c] = qc - fl;
-    gr[c] = 1.0 - fr[c];
-    o0[c] = (size_t)i0 * st[c];
-    o1[c] = (size_t)i1 * st[c];
-  }
-  double s[3] = {0.0, 0.0, 0.0}, ts = 0.0;
-#pragma unroll
-  for (int k = 0; k < (1 << C); ++k) {
-    const int bx = k & 1, by = (k >> 1) & 1, bz = (k >> 2) & 1;
-    double wt;
-    size_t o;
-    if (C == 3) {
-      wt = ((bz ? fr[2] : gr[2]) * (by ? fr[1] : gr[1])) * (bx ? fr[0] : gr[0]);
-      o = (bz ? o1[2] : o0[2]) + (by ? o1[1] : o0[1]) + (bx ? o1[0] : o0[0]);
-    } else {
-      wt = (by ? fr[1] : gr[1]) * (bx ? fr[0] : gr[0]);
-      o = (by ? o1[1] : o0[1]) + (bx ? o1[0] : o0[0]);
-    }
+  for (int c = 0; c < C; ++c) qc[c] = q[c];  // (a 2-D caller's q[2] is not set: it is not read)
+  fs::clamp_to_grid<C>(qc, e);
+  fs::corners64<C>(qc, e, [&](double wt, size_t o) {
     double cv[3] = {0.0, 0.0, 0.0}, ct = 0.0;
     src.template corner<C, WV, WT>(o, cv, ct);
     if (WV) {
@@ -132,7 +99,7 @@ __device__ __forceinline__ void gather(const Src& src, const LP& a, const double
       for (int c = 0; c < C; ++c) s[c] = s[c] + wt * cv[c];
     }
     if (WT) ts = ts + wt * ct;
-  }
+  });
 #pragma unroll
   for (int c = 0; c < C; ++c) v[c] = s[c];
   t = ts;

@@ -263,8 +263,6 @@ int check_volumes(int K, int D, int H, int W, long long sstride) {
   return FS_OK;
 }
 
-inline bool pos_finite(double v) { return v > 0.0 && v < HUGE_VAL; }
-
 template <int MODE>
 void launch_ray(bool with_skip, dim3 grid, hipStream_t s, const RP& f) {
   if (with_skip)
@@ -307,14 +305,14 @@ extern "C" int fs_raycast3d(const float* volumes, int K, int D, int H, int W, lo
   if (Hi < 1 || Wi < 1 || Hi > 65535 * kTile || Wi > 65535 * kTile) return FS_ERR_SHAPE;
   if (n < 2 || n > FS_RC_MAX_TF) return FS_ERR_SHAPE;
   if (mode != FS_RC_DVR && mode != FS_RC_MIP) return FS_ERR_ARG;
-  if (!(lo < hi) || !(lo > -HUGE_VAL) || !(hi < HUGE_VAL) || !pos_finite(dt) || !(t_min >= 0.0 && t_min < 1.0))
+  if (!(lo < hi) || !(lo > -HUGE_VAL) || !(hi < HUGE_VAL) || !fs::pos_finite(dt) || !(t_min >= 0.0 && t_min < 1.0))
     return FS_ERR_ARG;
   if (((uintptr_t)tf | (uintptr_t)image) & 15u) return FS_ERR_ARG;
   RP f;
   const int N[3] = {W, H, D};
   double reach = 0.0;
   for (int a = 0; a < 3; ++a) {
-    if (!pos_finite(spacing[a])) return FS_ERR_ARG;
+    if (!fs::pos_finite(spacing[a])) return FS_ERR_ARG;
     f.N[a] = N[a];
     f.nb[a] = nbricks(N[a]);
     f.ih[a] = (float)(1.0 / spacing[a]);
@@ -322,8 +320,9 @@ extern "C" int fs_raycast3d(const float* volumes, int K, int D, int H, int W, lo
   }
   const float inv_range = (float)(1.0 / (hi - lo));
   // (what is finite and positive in fp64 must still be so in fp32)
-  if (!(reach / dt <= (double)FS_RC_MAX_STEPS) || !pos_finite((float)dt) || !pos_finite(f.ih[0]) ||
-      !pos_finite(f.ih[1]) || !pos_finite(f.ih[2]) || !pos_finite(inv_range) || !pos_finite((float)(1.0 / dt)))
+  if (!(reach / dt <= (double)FS_RC_MAX_STEPS) || !fs::pos_finite((float)dt) || !fs::pos_finite(f.ih[0]) ||
+      !fs::pos_finite(f.ih[1]) || !fs::pos_finite(f.ih[2]) || !fs::pos_finite(inv_range) ||
+      !fs::pos_finite((float)(1.0 / dt)))
     return FS_ERR_ARG;
   f.vol = volumes; f.sstride = sstride; f.cams = cameras; f.tf = tf; f.skip = brick_range ? ws : nullptr;
   f.img = image; f.counts = counts;

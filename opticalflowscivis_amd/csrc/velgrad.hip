@@ -63,24 +63,6 @@ __device__ __forceinline__ double lmed3(const double (&m)[6]) {
   return ldexp(med3(a00, a11, a22), e);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // how statistic n of the summary combines: 0 sum, 1 minimum, 2 maximum
 __host__ __device__ constexpr int stat_op(int n) { return n < 4 ? 0 : (n - 4) % 4 == 2 ? 1 : (n - 4) % 4 == 3 ? 2 : 0; }
 
@@ -236,7 +218,8 @@ __global__ __launch_bounds__(NT) void velgrad_kernel(const float* __restrict__ f
     v[4 + 4 * n] = st[n].s1; v[5 + 4 * n] = st[n].s2; v[6 + 4 * n] = st[n].mn; v[7 + 4 * n] = st[n].mx;
   }
 #pragma unroll
-  for (int n = 0; n < NS; ++n) v[n] = stat_op(n) == 1 ? wave_min(v[n]) : stat_op(n) == 2 ? wave_max(v[n]) : wave_sum(v[n]);
+  for (int n = 0; n < NS; ++n)
+    v[n] = stat_op(n) == 1 ? fs::wave_min(v[n]) : stat_op(n) == 2 ? fs::wave_max(v[n]) : fs::wave_sum(v[n]);
   __shared__ double red[NT / 64][NS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) {
@@ -290,8 +273,6 @@ int plan(bool is3d, int C, int D, int H, int W, VP& f) {
   return FS_OK;
 }
 
-inline bool pos_finite(double v) { return v > 0.0 && v < HUGE_VAL; }
-
 template <int C>
 void launch_main(bool l2, dim3 grid, hipStream_t s, const float* flows, float* out, unsigned char* flags, double* ws,
                  const VP& f) {
@@ -315,10 +296,10 @@ int launch(bool is3d, const float* flows, int K, int C, int D, int H, int W, lon
   for (int c = 0; c < 3; ++c) {
     f.ih[c] = c < C ? inv_h[c] : 0.0;
     f.i2h[c] = c < C ? inv_2h[c] : 0.0;
-    if (c < C && !(pos_finite(f.ih[c]) && pos_finite(f.i2h[c]))) return FS_ERR_ARG;
+    if (c < C && !(fs::pos_finite(f.ih[c]) && fs::pos_finite(f.i2h[c]))) return FS_ERR_ARG;
   }
   for (int k = 0; k < K; ++k)
-    if (!pos_finite(scale[k])) return FS_ERR_ARG;
+    if (!fs::pos_finite(scale[k])) return FS_ERR_ARG;
   f.sstride = sstride;
   f.fields = fields;
   int np = 0;
