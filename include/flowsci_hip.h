@@ -1242,7 +1242,8 @@ int fs_series_encode(const float* src, int N, int C, int Dp, int Hp, int Wp, voi
  * has one channel.  Zero-padded (2r+1)^3 neighbourhood, u = v[n] - v[c], t = u / sqrt(0.81 + u^2),
  *   dist[c] = sum over the (2r+1)^3 taps of (t1 - t2)^2 / (0.1 + (t1 - t2)^2).
  *   vol1, vol2, dist, grad_* [B,1,D,H,W] fp32 contiguous; every extent >= 1 is legal.  radius 1, 2 or 3 (FS_ERR_ARG
- *   otherwise).  FS_ERR_SHAPE: B * ceil(D / 8) or ceil(H / 16) above 65535.
+ *   otherwise).  FS_ERR_SHAPE: B * ceil(D / 8) or ceil(H / 16) above 65535.  Bitwise equal vol1 and vol2 give a dist and
+ *   gradients of exactly 0; a voxel's 2r+1 taps along D are summed first, then added to its sum.
  * bwd: grad_vol1 / grad_vol2 (nullable, overwritten) = d sum(grad_dist * dist) / d vol1, vol2; gather-formulated, no
  * atomics, bit-reproducible.  The loss is fs_robust_sum(dist, ...) as in 2-D.
  */

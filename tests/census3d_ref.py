@@ -7,20 +7,25 @@ import torch.nn.functional as F
 
 def census3d_dist(vol1, vol2, radius):
     """[B,1,D,H,W] x 2 -> [B,1,D,H,W]: sum over the zero-padded (2r+1)^3 neighbourhood of (t1 - t2)^2 / (0.1 +
-    (t1 - t2)^2), t = u / sqrt(0.81 + u^2), u = v[neighbour] - v[centre] (UPFlow/utils/loss.py:59-71 on volumes)."""
+    (t1 - t2)^2), t = u / sqrt(0.81 + u^2), u = v[neighbour] - v[centre] (UPFlow/utils/loss.py:59-71 on volumes).
+    The taps are summed by torch.sum, plane by plane, not added one by one to a running sum: on float32 operands (the
+    fp32 oracle of tests/unsup3d_ledger_inputs.py) a border voxel's hundreds of equal padding terms would otherwise be
+    rounded the same way each time, an error of the summation order and not of the inputs."""
     r = radius
     D, H, W = vol1.shape[2:]
     p1, p2 = F.pad(vol1, [r] * 6), F.pad(vol2, [r] * 6)
-    dist = torch.zeros_like(vol1)
+    planes = []
     for dz in range(2 * r + 1):
+        taps = []
         for dy in range(2 * r + 1):
             for dx in range(2 * r + 1):
                 u1 = p1[:, :, dz:dz + D, dy:dy + H, dx:dx + W] - vol1
                 u2 = p2[:, :, dz:dz + D, dy:dy + H, dx:dx + W] - vol2
                 t1, t2 = u1 / torch.sqrt(0.81 + u1 ** 2), u2 / torch.sqrt(0.81 + u2 ** 2)
                 d = (t1 - t2) ** 2
-                dist = dist + d / (0.1 + d)
-    return dist
+                taps.append(d / (0.1 + d))
+        planes.append(torch.stack(taps).sum(0))
+    return torch.stack(planes).sum(0)
 
 
 def census3d_loss(vol1, vol2, radius, q=0.4):

@@ -6,11 +6,10 @@ import pytest
 import torch
 
 import census3d_ref as ref
+from ledger_harness import Guarded
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GUARD = 4096
-NAN_BITS = 0x7FC0DEAD  # a quiet NaN no kernel produces
 VAL_TOL, GRAD_TOL = 1e-5, 2e-4
 
 # the kernel's brick is 8 x 16 x 32 (z, y, x): one brick exactly, one brick + 1 along every axis, W % 4 != 0 with B = 2,
@@ -77,20 +76,6 @@ def test_z_constant_volume_is_seven_times_the_2d_kernel():
         dev = float((got[:, :, z] - want).abs().max())
         print("z = %d: largest deviation %.3g of the largest value" % (z, dev / scale))
         assert dev <= VAL_TOL * scale, (z, dev, scale)
-
-
-class Guarded:
-    """n floats between two guard bands of NAN_BITS; the interior starts as NAN_BITS too."""
-
-    def __init__(self, n):
-        self.n = int(n)
-        self.buf = torch.empty(self.n + 2 * GUARD, dtype=torch.float32, device=DEV)
-        self.buf.view(torch.int32).fill_(NAN_BITS)
-        self.t = self.buf[GUARD:GUARD + self.n]
-
-    def intact(self):
-        b = self.buf.view(torch.int32)
-        return bool((b[:GUARD] == NAN_BITS).all()) and bool((b[GUARD + self.n:] == NAN_BITS).all())
 
 
 @pytest.mark.parametrize("radius", [1, 3])
