@@ -61,8 +61,10 @@ enum {
  *        intensity through a transfer function, with per-brick value ranges to jump over empty space).
  *   450  fs_iso_count3d / fs_iso_emit3d / fs_iso3d_ws_bytes (volumes to indexed triangle meshes: marching tetrahedra).
  *   460  fs_lic2d / fs_lic3d and their _ws_bytes queries (line integral convolution: a texture averaged along the
- *        streamlines of step flows). */
-#define FS_ABI_VERSION 460
+ *        streamlines of step flows).
+ *   470  fs_critical_count{2,3}d / fs_critical_emit{2,3}d and their _ws_bytes queries (critical points of step flows:
+ *        where the piecewise-linear field vanishes, with its Jacobian, invariants and class). */
+#define FS_ABI_VERSION 470
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -1168,6 +1170,94 @@ int fs_lic2d(const float* flows, int K, int C, int H, int W, long long flow_sstr
 int fs_lic3d(const float* flows, int K, int C, int D, int H, int W, long long flow_sstride, const float* tex,
              long long tex_sstride, const double* weights, int L, double h, double vmin, int method, float* out,
              unsigned char* ends, int* count, void* ws, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Critical points -- where K step flows vanish and what kind of zero each is (source, sink, saddle, spiral): the zeros
+ * of the piecewise-linear field on the Kuhn split of every cell, with the Jacobian of the affine piece, its invariants
+ * and its class.  Two passes with the caller's prefix sum between them, shaped like the isosurface pair.
+ *   flows: as for fs_velgrad*: K fields of C fp32 planes of D*H*W elements (2-D: D = 1, C = 2; 3-D: C = 3), field k at
+ *     + k * flow_sstride elements (>= C*D*H*W: every other field of a stack is read in place), node (z, y, x) at
+ *     (z * H + y) * W + x; component 0 and axis 0 run along x (W), 1 along y, 2 along z.  Every extent >= 2.
+ *   inv_h: HOST array of C doubles, 1 / h_c; scale: HOST array of K doubles, velocity = displacement * scale[k]; all
+ *     finite and positive.  The scales travel in the launches' arguments: nothing is copied to the device.
+ *     vmin >= 0, finite, rounded to fp32 once.
+ *   All arithmetic below is fp64 on the widened fp32 values, without fused multiply-adds, in exactly the written order
+ *   (a restatement with the same operations in the same order reproduces every bit but vmax's square root;
+ *   tests/critical_ref.py).
+ *   Simplices.  A cell is a node whose coordinates are all below extent - 1; corner c of it sits at the offset
+ *     (dz, dy, dx) = (c >> 2 & 1, c >> 1 & 1, c & 1).
+ *     3-D: the six tetrahedra of the isosurface section: one per permutation pi of the axes (x = 0, y = 1, z = 2) in
+ *       lexicographic order, t = 0..5, with the corners c0 = the cell's node, c1 = c0 + e_pi0, c2 = c1 + e_pi1,
+ *       c3 = c0 + (1,1,1).
+ *     2-D: two triangles: t = 0 is pi = (x, y) with c0, c0 + ex, c0 + ex + ey; t = 1 is pi = (y, x) with c0, c0 + ey,
+ *       c0 + ex + ey.
+ *     The corners of a simplex are in increasing linear node index; the definition rests on this.
+ *   Per simplex with corner values v0..vC (C-vectors), in this order:
+ *     1. A cell with a corner that has a component that is not finite is NONFINITE: none of its simplices counts or
+ *        emits anything.
+ *     2. Every corner with (vx^2 + vy^2) + vz^2 <= ((double)(float)vmin)^2 (2-D: vx^2 + vy^2): QUIET, nothing.  With
+ *        vmin = 0 an all-zero simplex is quiet.
+ *     3. Some component > 0 at all corners, or < 0 at all corners: no point.
+ *     4. The face minors m_i = the determinant of the corners other than i, in increasing corner number:
+ *          det3(a,b,c) = (a0*(b1*c2 - b2*c1) - a1*(b0*c2 - b2*c0)) + a2*(b0*c1 - b1*c0);  det2(a,b) = a0*b1 - a1*b0
+ *        and s_i = (-1)^i m_i.  Two simplices that share a face, in one cell or across cells, evaluate the same
+ *        expression on the same nodes in the same order: the minor is the same bits in both, so a zero near a shared
+ *        face belongs to exactly one of them.
+ *     5. Some s_i is 0 or not finite: the simplex is DEGENERATE; it is counted and emits nothing.
+ *     6. All s_i > 0 or all s_i < 0: the simplex holds one critical point.  Otherwise none.
+ *   Per point:
+ *     S = ((s0 + s1) + s2) + s3,  l_i = s_i / S            (2-D: S = (s0 + s1) + s2)
+ *     o0 = (l1 + l2) + l3,  o1 = l2 + l3,  o2 = l3         (2-D: o0 = l1 + l2, o1 = l2)
+ *     coordinate along axis pi_k = (double)i_pik + o_k;  position = (float)(coordinate / inv_h[axis]), stored (x, y(, z)).
+ *     J[r][pi_k] = (((double)v_{k+1,r} - (double)v_{k,r}) * inv_h[pi_k]) * scale[step], stored fp64 [C*C] at r * C + c.
+ *     3-D: P = (J00 + J11) + J22;
+ *          Q = ((J00*J11 - J01*J10) + (J00*J22 - J02*J20)) + (J11*J22 - J12*J21);   R = det3(row 0, row 1, row 2);
+ *          Delta = (((((18 P) Q) R - (4 ((P P) P)) R) + (P P) (Q Q)) - 4 ((Q Q) Q)) - 27 (R R);   inv = (P, Q, R, Delta).
+ *          n_pos (eigenvalues with a positive real part, by Routh-Hurwitz):  R > 0: 3 if (P > 0 and P*Q > R) else 1;
+ *          R < 0: 0 if (P < 0 and P*Q < R) else 2;  else 0.
+ *     2-D: tr = J00 + J11, det = J00*J11 - J01*J10, disc = tr*tr - 4*det;   inv = (tr, det, disc, 0).
+ *          n_pos = 1 if det < 0; 2 if det > 0 and tr > 0; else 0.
+ *     cls (uint8) = n_pos | FS_CP_SPIRAL (Delta < 0; 2-D: disc < 0) | FS_CP_DEGENERATE (R, 2-D: det, equal to 0, or an
+ *       invariant not finite; n_pos is then 0) | FS_CP_MARGINAL (3-D: P*Q == R; 2-D: det > 0 and tr == 0).
+ *       The Poincare index is the sign of R (det).
+ *     vmax = (float)(sqrt(the largest of the corners' sums of step 2) * scale[step]).
+ *   The points of a step are ordered by cell index, then by t.  Bitwise reproducible: no atomic decides a value or an
+ *   order.
+ *
+ * fs_critical_count{2,3}d -- one launch for all K steps.  ws: fs_critical{2,3}d_ws_bytes bytes, 16-byte aligned, written as
+ *     int32 np[K*D*H], int32 ndeg[K*D*H]: per row (k, z, y) the points and the degenerate simplices of its cells;
+ *     padding to a multiple of 16 bytes;  uint8 mask[K][D*H*W], one byte per cell's origin node (0 for a node that is no
+ *     cell's origin): bit t = simplex t holds a point, FS_CP_MASK_DEGENERATE = the cell has a degenerate simplex,
+ *     FS_CP_MASK_NONFINITE = a corner is not finite (no other bit is then set).
+ * The caller turns np into row_offsets, int64 [K*D*H + 1] in DEVICE memory: the exclusive prefix sum over all rows with
+ *   the total N at the end.
+ * fs_critical_emit{2,3}d -- one launch per few hundred steps (none when N = 0).  It recomputes every row's
+ *   in-row prefix from the masks; a point is row (row offset + in-row prefix at its cell + rank of t in the cell's mask)
+ *   of cell int32 [N] (the origin's node index within its step), simplex uint8 [N], pos fp32 [N][C], jac fp64 [N][C*C],
+ *   inv fp64 [N][4], cls uint8 [N] and vmax fp32 [N].  Nothing is written at or beyond row N.  status: int32 [1], zeroed
+ *   by the CALLER; bit 0 is set when the masks and the offsets disagree -- the outputs are then not a table.
+ *   FS_ERR_NULLPTR: flows, ws (inv_h, scale, row_offsets, status) NULL; an output with N > 0.  FS_ERR_SHAPE: K < 1 or
+ *   K*D*H above 2^31 - 1, C other than 2 (2-D) / 3 (3-D), an extent below 2, 2^31 - 1 nodes or more, flow_sstride below
+ *   C*D*H*W.  FS_ERR_ARG: an inv_h[c] or scale[k] that is not finite or not positive, vmin negative or not finite (as
+ *   fp32), N negative, ws not 16-byte aligned.  All of them are returned before anything is launched; the _ws_bytes
+ *   queries launch nothing and return the byte count or -(FS_ERR_*).
+ */
+enum { FS_CP_NPOS_MASK = 3, FS_CP_SPIRAL = 4, FS_CP_DEGENERATE = 8, FS_CP_MARGINAL = 16 };
+enum { FS_CP_MASK_DEGENERATE = 64, FS_CP_MASK_NONFINITE = 128 };
+long long fs_critical2d_ws_bytes(int K, int H, int W);
+long long fs_critical3d_ws_bytes(int K, int D, int H, int W);
+int fs_critical_count2d(const float* flows, int K, int C, int H, int W, long long flow_sstride, double vmin,
+                        unsigned char* ws, fs_stream_t stream);
+int fs_critical_count3d(const float* flows, int K, int C, int D, int H, int W, long long flow_sstride, double vmin,
+                        unsigned char* ws, fs_stream_t stream);
+int fs_critical_emit2d(const float* flows, int K, int C, int H, int W, long long flow_sstride, const double* inv_h,
+                       const double* scale, double vmin, const unsigned char* ws, const long long* row_offsets, long long N,
+                       int* cell, unsigned char* simplex, float* pos, double* jac, double* inv, unsigned char* cls,
+                       float* vmax, int* status, fs_stream_t stream);
+int fs_critical_emit3d(const float* flows, int K, int C, int D, int H, int W, long long flow_sstride, const double* inv_h,
+                       const double* scale, double vmin, const unsigned char* ws, const long long* row_offsets, long long N,
+                       int* cell, unsigned char* simplex, float* pos, double* jac, double* inv, unsigned char* cls,
+                       float* vmax, int* status, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

@@ -1,0 +1,310 @@
+"""Critical points: where a series' estimated step flows vanish, what kind of zero each is -- source, sink, saddle,
+spiral -- and which zero of one step is which of the next.  They are the skeleton of vector-field topology, what one reads
+a LIC picture for, and what `regions` (thresholded Q / lambda2) cannot see: stagnation points, the saddles between
+vortices, separation and attachment points.  Shared by the flow2d / flow3d / upflow `critical` entry points:
+
+    python -m opticalflowscivis_amd.flow2d.critical --dataset rectangle2d --png-dir shots --json r.json
+    python -m opticalflowscivis_amd.flow3d.critical --flows flows.npy --link-radius 2 --out cp.npz --json r.json
+    python -m opticalflowscivis_amd.upflow.critical --seq frames.npy --classes saddle,focus_sink --vmin 0.05
+
+The step flows are those of `trace`, `vortex` and `lic` (stepflows.step_chain over the flows flow_eval extracts, or
+--flows); each is taken as a steady field, piecewise linear on the Kuhn split of its cells.  ops.critical_points finds
+the zeros of `--chunk` steps in two launches; the per-step tables stay on the host, where the filters (--min-jnorm,
+--classes; --vmin goes to the kernel) and the linking of consecutive steps (link_points: mutual nearest neighbours of
+equal n_pos within --link-radius) are plumbing.  --out holds every column of the table, `offsets`, `track` and `frames`;
+--json the per-step rows; --png-dir (2-D) one picture per step with a marker per point, coloured by class.
+
+Out of scope: separatrices and full topological skeletons; higher-order critical points and those of the trilinear
+interpolant of a cell; simulation-of-simplicity handling of exact ties (a simplex with a face minor of exactly 0 is
+reported as `degenerate`, not resolved); periodic domains; tracking through space-time cells (steps are linked by
+distance); autograd through the op."""
+import argparse
+import itertools
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import ops, stepflows
+
+COLUMNS = ("cell", "simplex", "pos", "jac", "inv", "cls", "vmax")
+# marker colours (RGB) by n_pos; a spiral / focus is drawn lighter
+_COLOURS = {2: ((40, 90, 255), (40, 220, 60), (255, 50, 40)), 3: ((40, 90, 255), (40, 220, 60), (255, 200, 40), (255, 50, 40))}
+
+
+def link_points(tables, radius):
+    """Link the points of consecutive steps.  tables: one dict per step with pos ([n, nd], physical units) and cls
+    ([n] uint8).  A point of step j and one of step j + 1 with equal n_pos whose distance is <= radius are linked when
+    each is the other's nearest such point; ties go to the lower row.  The points are binned by a uniform grid a hair
+    wider than the radius, so only the 3^nd bins around a point are searched.
+
+    Returns (track, births, deaths): track, one int64 array per step -- a linked point inherits its predecessor's id,
+    any other gets a new one, ids counting up from 0 in the order of steps and rows; births[j], the points of step j
+    without a predecessor (all of step 0); deaths[j], the points of step j without a successor (0 for the last step,
+    which has no next one).  radius <= 0 links nothing."""
+    radius = float(radius)
+    track, births, deaths = [], [], []
+    next_id = 0
+    prev = None
+    for j, tab in enumerate(tables):
+        pos = np.asarray(tab["pos"], dtype=np.float64)
+        n = len(pos)
+        ids = np.full(n, -1, dtype=np.int64)
+        if prev is not None and n and len(prev[0]) and radius > 0:
+            npos = np.asarray(tab["cls"]).astype(np.int64) & ops.CP_NPOS_MASK
+            fwd = _nearest(prev[0], prev[1], pos, npos, radius)
+            bwd = _nearest(pos, npos, prev[0], prev[1], radius)
+            linked = np.nonzero(bwd >= 0)[0]
+            linked = linked[fwd[bwd[linked]] == linked]
+            ids[linked] = track[-1][bwd[linked]]
+            deaths.append(len(prev[0]) - len(linked))
+        elif prev is not None:
+            deaths.append(len(prev[0]))
+        new = np.nonzero(ids < 0)[0]
+        ids[new] = next_id + np.arange(len(new), dtype=np.int64)
+        next_id += len(new)
+        births.append(len(new))
+        track.append(ids)
+        prev = (pos, np.asarray(tab["cls"]).astype(np.int64) & ops.CP_NPOS_MASK)
+    if tables:
+        deaths.append(0)
+    return track, births, deaths
+
+
+def _nearest(a, ka, b, kb, radius):
+    """For every row of a [n, nd] the row of b nearest to it among those with the same key and a distance <= radius
+    (the lowest row on a tie), or -1."""
+    nd = a.shape[1]
+    out = np.full(len(a), -1, dtype=np.int64)
+    bins = {}
+    edge = radius * (1.0 + 1e-9)  # (a pair exactly `radius` apart must not end two bins apart by the divisions' rounding)
+    for key, rows in _groups(np.concatenate([np.floor(b / edge).astype(np.int64), kb[:, None]], 1)):
+        bins[key] = rows
+    r2 = radius * radius
+    offsets = list(itertools.product((-1, 0, 1), repeat=nd))
+    for key, rows in _groups(np.concatenate([np.floor(a / edge).astype(np.int64), ka[:, None]], 1)):
+        cand = [bins[k] for k in (tuple(key[i] + o[i] for i in range(nd)) + (key[nd],) for o in offsets) if k in bins]
+        if not cand:
+            continue
+        cand = np.sort(np.concatenate(cand))
+        d2 = ((a[rows][:, None, :] - b[cand][None, :, :]) ** 2).sum(-1)
+        best = d2.argmin(1)  # (the first minimum: the lowest row)
+        ok = d2[np.arange(len(rows)), best] <= r2
+        out[rows[ok]] = cand[best[ok]]
+    return out
+
+
+def _groups(keys):
+    """(key tuple, ascending rows) of every distinct row of the integer array keys [n, m]."""
+    if not len(keys):
+        return
+    order = np.lexsort(keys.T[::-1])
+    s = keys[order]
+    cut = np.nonzero((s[1:] != s[:-1]).any(1))[0] + 1
+    for rows in np.split(order, cut):
+        yield tuple(int(v) for v in keys[rows[0]]), np.sort(rows)
+
+
+def parse_classes(text, nd):
+    """The set of class names of a comma-separated list, or None for all."""
+    if not text:
+        return None
+    names = [n.strip() for n in text.split(",") if n.strip()]
+    known = ops.critical_class_list(nd)
+    unknown = [n for n in names if n not in known]
+    if unknown:
+        raise ValueError("unknown class(es) %r: choose among %s" % (unknown, ", ".join(known)))
+    return set(names)
+
+
+def critical_series(step_flows, n_steps, sp, spacing=1.0, vmin=0.0, chunk=4, frames=None, dt=1.0, min_jnorm=0.0,
+                    classes=None, link_radius=0.0):
+    """The critical points of the n_steps step flows that step_flows(j0, j1) -> [j1 - j0, C, *sp] hands out `chunk` at a
+    time (each exactly once, one ops.critical_points call per chunk).  frames: the n_steps + 1 frames the chain visits
+    (default 0..n_steps); a step's velocities are its displacements / (frames spanned * dt).  Filters, applied on the
+    host to every column alike: min_jnorm (the Frobenius norm of the Jacobian) and classes (a set of
+    ops.critical_class_names names, None for all); vmin goes to the kernel.  link_radius: see link_points.
+
+    Returns a dict: tables (one dict of host arrays per step: cell, simplex, pos, jac, inv, cls, vmax), track (one int64
+    array per step), steps (one dict per step: step, t_from, t_to, scale, n_found -- what the kernel found --, n_points
+    -- what the filters kept --, classes {name: count}, degenerate_simplices, nonfinite_cells, index_sum -- the sum of
+    the kept points' Poincare indices --, births, deaths) and the totals time_flows_s, time_kernel_s."""
+    chunk = max(1, int(chunk))
+    n_steps = int(n_steps)
+    sp = tuple(int(s) for s in sp)
+    nd = len(sp)
+    frames = list(range(n_steps + 1)) if frames is None else list(frames)
+    if len(frames) != n_steps + 1:
+        raise ValueError("frames must name the %d frames the chain visits, got %d" % (n_steps + 1, len(frames)))
+    scales = stepflows.step_scales(frames, dt) if n_steps else []
+    min_jnorm = float(min_jnorm)
+    if not (0 <= min_jnorm < float("inf")):
+        raise ValueError("min_jnorm must be finite and >= 0, got %r" % (min_jnorm,))
+    rows = [{"step": j, "t_from": frames[j], "t_to": frames[j + 1], "scale": scales[j]} for j in range(n_steps)]
+    tables = []
+    t_flows = t_kernel = 0.0
+    for j0 in range(0, n_steps, chunk):
+        j1 = min(n_steps, j0 + chunk)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f = step_flows(j0, j1)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        r = ops.critical_points(f, spacing, scales[j0:j1], vmin)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        t_flows += t1 - t0
+        t_kernel += t2 - t1
+        ops.critical_points_check(r)
+        off = r["offsets"].cpu().numpy()
+        counts = r["counts"].cpu().numpy()
+        host = {c: r[c].cpu().numpy() for c in COLUMNS}
+        for j in range(j0, j1):
+            a, b = int(off[j - j0]), int(off[j - j0 + 1])
+            tab = {c: host[c][a:b] for c in COLUMNS}
+            names = np.array(ops.critical_class_names(tab["cls"], nd), dtype=object)
+            keep = np.ones(b - a, dtype=bool)
+            if min_jnorm > 0:
+                keep &= np.sqrt((tab["jac"] ** 2).sum(1)) >= min_jnorm
+            if classes is not None:
+                keep &= np.array([n in classes for n in names], dtype=bool)
+            tab = {c: np.ascontiguousarray(v[keep]) for c, v in tab.items()}
+            names = names[keep]
+            sign = np.sign(tab["inv"][:, 2 if nd == 3 else 1])
+            rows[j].update(n_found=b - a, n_points=int(keep.sum()),
+                           classes={n: int((names == n).sum()) for n in ops.critical_class_list(nd)},
+                           degenerate_simplices=int(counts[j - j0, 1]), nonfinite_cells=int(counts[j - j0, 2]),
+                           index_sum=int(np.nan_to_num(sign).sum()))
+            tables.append(tab)
+        del f, r
+    track, births, deaths = link_points(tables, link_radius)
+    for j, row in enumerate(rows):
+        row.update(births=births[j], deaths=deaths[j])
+    return {"tables": tables, "track": track, "steps": rows, "time_flows_s": t_flows, "time_kernel_s": t_kernel}
+
+
+def table_arrays(res, nd, frames):
+    """The arrays of --out: every column of the per-step tables joined, `step` (int32 [N]), `offsets` (int64 [K + 1]),
+    `track` (int64 [N]) and `frames` (int64 [K + 1])."""
+    tabs = res["tables"]
+    empty = {"cell": np.zeros(0, np.int32), "simplex": np.zeros(0, np.uint8), "pos": np.zeros((0, nd), np.float32),
+             "jac": np.zeros((0, nd * nd), np.float64), "inv": np.zeros((0, 4), np.float64), "cls": np.zeros(0, np.uint8),
+             "vmax": np.zeros(0, np.float32)}
+    out = {c: np.concatenate([t[c] for t in tabs]) if tabs else empty[c] for c in COLUMNS}
+    n = [len(t["cell"]) for t in tabs]
+    out["offsets"] = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    out["step"] = np.repeat(np.arange(len(tabs), dtype=np.int32), n)
+    out["track"] = np.concatenate(res["track"]) if tabs else np.zeros(0, np.int64)
+    out["frames"] = np.asarray(frames, dtype=np.int64)
+    return out
+
+
+def draw_points(grey, tab, spacing):
+    """An RGB uint8 picture [H, W, 3]: `grey` ([H, W] in [0, 1]) with a plus-shaped marker at every
+    point of the 2-D table `tab`, coloured by n_pos (sink blue, saddle green, source red; a focus lighter; anything
+    degenerate or a center white)."""
+    from . import render
+    H, W = grey.shape
+    img = np.repeat(render.to_uint8(grey)[:, :, None], 3, axis=2)
+    hy, hx = spacing
+    for (x, y), c in zip(tab["pos"], tab["cls"]):
+        c = int(c)
+        col = np.array(_COLOURS[2][c & ops.CP_NPOS_MASK], dtype=np.int64)
+        if c & ops.CP_SPIRAL:
+            col = (col + 255) // 2
+        if c & (ops.CP_DEGENERATE | ops.CP_MARGINAL):
+            col = np.array((255, 255, 255))
+        px, py = int(round(float(x) / hx)), int(round(float(y) / hy))
+        for dy, dx in ((0, 0), (0, 1), (0, -1), (1, 0), (-1, 0)):
+            if 0 <= py + dy < H and 0 <= px + dx < W:
+                img[py + dy, px + dx] = col
+    return img
+
+
+def _args(nd, desc, model):
+    ap = argparse.ArgumentParser(description=desc)
+    stepflows.add_source_args(ap, nd, model, direction="fwd: the flows t -> t+1; bwd: the model's own backward flows, from "
+                              "the last frame down", chunk="step flows estimated at a time and handed to one call",
+                              dt="the time one frame spans: velocity = displacement / (frames spanned * dt)", spacing=True)
+    ap.add_argument("--vmin", type=float, default=0.0, help="a simplex whose corners all move at most this far per step "
+                    "(in elements) holds no point")
+    ap.add_argument("--min-jnorm", type=float, default=0.0, help="drop points whose Jacobian's Frobenius norm is below this")
+    ap.add_argument("--classes", default=None, help="keep only these classes: comma-separated, out of %s" %
+                    ",".join(ops.critical_class_list(nd)))
+    ap.add_argument("--link-radius", type=float, default=2.0, help="link points of consecutive steps that are each "
+                    "other's nearest of equal n_pos within this distance (physical units); 0: no linking")
+    ap.add_argument("--out", default=None, metavar="CP.npz", help="write the table (%s, step, offsets, track, frames) here" %
+                    ", ".join(COLUMNS))
+    if nd == 2:
+        ap.add_argument("--png-dir", default=None, help="write one picture per step, critical_%%03d_to_%%03d.png, here: a "
+                        "marker per point over the step's first frame")
+    return ap
+
+
+def check_args(args):
+    """What the parser cannot express."""
+    stepflows.check_source_args(args)
+    if not (0 <= args.vmin < float("inf")):
+        raise SystemExit("--vmin must be finite and >= 0")
+    if not (0 <= args.min_jnorm < float("inf")):
+        raise SystemExit("--min-jnorm must be finite and >= 0")
+    if not (0 <= args.link_radius < float("inf")):
+        raise SystemExit("--link-radius must be finite and >= 0")
+    try:
+        parse_classes(args.classes, args.nd)
+    except ValueError as e:
+        raise SystemExit("--classes: %s" % e)
+    return args
+
+
+def run(args, nd, model, make_model):
+    """The critical points of one parsed command line.  make_model() -> flows(frames, pairs) -> [2P, C, *sp]."""
+    from . import render
+    sf = stepflows.open_step_flows(args, nd, model, make_model, torch.device("cuda"))
+    name, sp, visited, K = sf.name, sf.sp, sf.visited, sf.n_steps
+    spacing = args.spacing[0] if len(args.spacing) == 1 else tuple(args.spacing)
+    res = critical_series(sf.source, K, sp, spacing, args.vmin, args.chunk, frames=visited or [0], dt=args.dt,
+                          min_jnorm=args.min_jnorm, classes=parse_classes(args.classes, nd), link_radius=args.link_radius)
+    doc = {"sequence": name, "shape": list(sp), "model": None if args.flows else args.model, "direction": args.direction,
+           "chunk": args.chunk, "gap": args.gap, "spacing": list(args.spacing), "dt": args.dt, "vmin": args.vmin,
+           "min_jnorm": args.min_jnorm, "classes": args.classes, "link_radius": args.link_radius, "frames": visited,
+           "steps": res["steps"], "n_tracks": int(sum(r["births"] for r in res["steps"])),
+           "time_inference_s": res["time_flows_s"], "time_kernel_s": res["time_kernel_s"]}
+    if not res["steps"]:
+        print("%s: the chain has no step" % name)
+    for w in res["steps"]:
+        kinds = "  ".join("%s %d" % (n, c) for n, c in w["classes"].items() if c)
+        print("%s %s frames %d -> %d: %d points (index sum %d)  %s  degenerate simplices %d  nonfinite cells %d  births %d  "
+              "deaths %d" % (name, args.direction, w["t_from"], w["t_to"], w["n_points"], w["index_sum"], kinds or "-",
+                             w["degenerate_simplices"], w["nonfinite_cells"], w["births"], w["deaths"]))
+    if res["steps"]:
+        print("flows %.3f s  kernel %.4f s" % (res["time_flows_s"], res["time_kernel_s"]))
+    png_dir = getattr(args, "png_dir", None)
+    if png_dir and res["steps"]:
+        os.makedirs(png_dir, exist_ok=True)
+        hs = list(args.spacing) * (2 if len(args.spacing) == 1 else 1)
+        doc["pngs"] = []
+        for j, w in enumerate(res["steps"]):
+            grey = np.zeros(sp, np.float32) if sf.frames is None else sf.frames[w["t_from"]].float().cpu().numpy()
+            path = os.path.join(png_dir, "critical_%03d_to_%03d.png" % (w["t_from"], w["t_to"]))
+            render.write_png(path, draw_points(grey, res["tables"][j], hs))
+            doc["pngs"].append(path)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "wb") as f:  # (a file object: numpy appends no suffix)
+            np.savez(f, **table_arrays(res, nd, visited or [0]))
+    stepflows.write_report(doc, args.json)
+    return doc
+
+
+def main_rife(Model, nd, argv=None):
+    """flow2d / flow3d: the steps m -> m+h (or back) of the final IFNet flows."""
+    args = check_args(_args(nd, "Critical points of the flows of a RIFE model", "rife").parse_args(argv))
+    return run(args, nd, "rife", stepflows.rife_model(Model, args))
+
+
+def main_upflow(make_net, argv=None):
+    """upflow: the steps t -> t+gap through flow_f_out, or back through flow_b_out."""
+    args = check_args(_args(2, "Critical points of UPFlow's flows", "upflow").parse_args(argv))
+    return run(args, 2, "upflow", stepflows.upflow_model(make_net, args))

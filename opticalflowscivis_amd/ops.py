@@ -3702,6 +3702,197 @@ def isosurface_check(result):
 
 
 # --------------------------------------------------------------------------------------------
+# Critical points: where step flows vanish, and what kind of zero each is (fs_critical_count{2,3}d, fs_critical_emit{2,3}d)
+# --------------------------------------------------------------------------------------------
+CP_NPOS_MASK, CP_SPIRAL, CP_DEGENERATE, CP_MARGINAL = 3, 4, 8, 16  # FS_CP_*: the bits of `cls`
+CP_MASK_DEGENERATE, CP_MASK_NONFINITE = 64, 128                    # FS_CP_MASK_*: of a cell's mask byte (bit t: simplex t)
+_CP_BASE = {2: ("sink", "saddle", "source"), 3: ("sink", "saddle1", "saddle2", "source")}
+
+
+def critical_class_names(cls, nd):
+    """The report name of every class byte in `cls` (a tensor, an array or a sequence) in nd dimensions: by n_pos, the
+    eigenvalues with a positive real part -- sink (0), saddle (2-D: 1), saddle1 / saddle2 (3-D: 1 / 2), source (nd) --
+    with the prefix "focus_" (2-D) / "spiral_" (3-D) when CP_SPIRAL is set; "degenerate" when CP_DEGENERATE is set, and
+    in 2-D "center" when CP_MARGINAL is (a purely rotating zero)."""
+    if nd not in (2, 3):
+        raise ValueError("nd must be 2 or 3, got %r" % (nd,))
+    vals = cls.reshape(-1).tolist() if hasattr(cls, "reshape") else list(cls)
+    names = []
+    for c in vals:
+        c = int(c)
+        if c & CP_DEGENERATE:
+            names.append("degenerate")
+        elif nd == 2 and c & CP_MARGINAL:
+            names.append("center")
+        else:
+            n = c & CP_NPOS_MASK
+            if n > nd:
+                raise ValueError("class %d has n_pos = %d in %d dimensions" % (c, n, nd))
+            names.append((("focus_" if nd == 2 else "spiral_") if c & CP_SPIRAL else "") + _CP_BASE[nd][n])
+    return names
+
+
+def critical_class_list(nd):
+    """Every name critical_class_names can give in nd dimensions, in report order."""
+    pre = "focus_" if nd == 2 else "spiral_"
+    names = list(_CP_BASE[nd]) + [pre + n for n in _CP_BASE[nd] if nd == 3 or n != "saddle"]
+    return names + (["center"] if nd == 2 else []) + ["degenerate"]
+
+
+def critical_points_cost(shape, K=1, N=0, op="count"):
+    """(HBM bytes, flops) the algorithm needs for one pass of ops.critical_points over K step flows of spatial `shape`
+    ((H,W) or (D,H,W)).  "count": every node's C components read once (4 C bytes), its mask byte written, two int32 per
+    row.  "emit": the mask bytes read and the N rows written (4 cell + 1 simplex + 4 C pos + 8 C^2 jac + 32 inv + 1 cls +
+    4 vmax); the corners gathered around flagged cells are on top and depend on the field.  The streaming work is
+    compares and integer work: flops count the fp64 minors and invariants of the N points only (~100 C per point)."""
+    sp, P = _lattice(shape)
+    C = len(sp)
+    K, N = int(K), int(N)
+    if K < 1 or N < 0:
+        raise ValueError("K >= 1 and N >= 0, got %d, %d" % (K, N))
+    rows = P // sp[-1]
+    if op == "count":
+        return K * (P * (4 * C + 1) + 8 * rows), 0
+    if op == "emit":
+        return K * P + N * (4 + 1 + 4 * C + 8 * C * C + 32 + 1 + 4), N * 100 * C
+    raise ValueError("op must be 'count' or 'emit', got %r" % (op,))
+
+
+def _cp_vmin(vmin):
+    try:
+        vmin = float(vmin)
+    except (TypeError, ValueError):
+        raise ValueError("vmin must be a number, got %r" % (vmin,))
+    if not 0 <= vmin < float("inf"):
+        raise ValueError("vmin must be finite and >= 0, got %r" % (vmin,))
+    return vmin
+
+
+def _cp_spacing_scale(spacing, scale, nd, K):
+    try:
+        hs = [float(v) for v in spacing] if hasattr(spacing, "__len__") else [float(spacing)] * nd
+        ss = [float(v) for v in scale] if hasattr(scale, "__len__") else [float(scale)] * K
+    except TypeError:
+        raise ValueError("spacing and scale must be numbers or sequences of numbers, got %r and %r" % (spacing, scale))
+    if len(hs) != nd or not all(0 < h < float("inf") for h in hs):
+        raise ValueError("spacing must be one or %d finite positive values, got %r" % (nd, spacing))
+    if len(ss) != K or not all(0 < v < float("inf") for v in ss):
+        raise ValueError("scale must be one or %d finite positive values, got %r" % (K, scale))
+    return hs, ss
+
+
+def critical_points_count(flows, vmin=0.0):
+    """The first pass of ops.critical_points on its own (fs_critical_count{2,3}d): the workspace (uint8: the per-row
+    counts of points and of degenerate simplices, then one mask byte per node) and row_offsets, int64 [K*D*H + 1] on the
+    device: the exclusive prefix sum of the rows' point counts (plumbing: torch.cumsum).  Never synchronises."""
+    vmin = _cp_vmin(vmin)
+    flows, nd = _advect_flows(flows)
+    sp, P = _lattice(flows.shape[2:])
+    K = int(flows.shape[0])
+    dev = flows.device
+    R = K * (P // sp[-1])
+    nb = getattr(_lib.lib(), "fs_critical%dd_ws_bytes" % nd)(K, *sp)
+    if nb < 0:
+        _lib.check(int(-nb), "fs_critical%dd_ws_bytes" % nd)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    nbytes, flops = critical_points_cost(sp, K, op="count")
+    with torch.cuda.device(dev):
+        _call("fs_critical_count%dd" % nd, flows.data_ptr(), K, nd, *sp, flows.stride(0) if K > 1 else nd * P, vmin,
+              ws.data_ptr(), _stream(flows), algo_bytes=nbytes, algo_flops=flops)
+    off = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(ws[:4 * R].view(torch.int32), 0, dtype=torch.int64)
+    return ws, off
+
+
+def critical_points_emit(flows, spacing, scale, vmin, ws, row_offsets, N):
+    """The second pass of ops.critical_points on its own (fs_critical_emit{2,3}d), on what critical_points_count returned
+    and the total N as a host int.  Returns a dict on the device: cell, simplex, pos, jac, inv, cls, vmax, status.
+    Never synchronises; launches nothing when N is 0."""
+    vmin = _cp_vmin(vmin)
+    flows, nd = _advect_flows(flows)
+    sp, P = _lattice(flows.shape[2:])
+    K = int(flows.shape[0])
+    hs, ss = _cp_spacing_scale(spacing, scale, nd, K)
+    dev = flows.device
+    N = int(N)
+    if N < 0:
+        raise ValueError("N must be >= 0, got %d" % N)
+    res = {"cell": torch.empty(N, dtype=torch.int32, device=dev), "simplex": torch.empty(N, dtype=torch.uint8, device=dev),
+           "pos": torch.empty((N, nd), dtype=torch.float32, device=dev),
+           "jac": torch.empty((N, nd * nd), dtype=torch.float64, device=dev),
+           "inv": torch.empty((N, 4), dtype=torch.float64, device=dev), "cls": torch.empty(N, dtype=torch.uint8, device=dev),
+           "vmax": torch.empty(N, dtype=torch.float32, device=dev), "status": torch.zeros(1, dtype=torch.int32, device=dev)}
+    if N:
+        nbytes, flops = critical_points_cost(sp, K, N, op="emit")
+        # component 0 and axis 0 run along x: the tensor's last axis
+        inv_h = (ctypes.c_double * nd)(*[1.0 / h for h in hs[::-1]])
+        with torch.cuda.device(dev):
+            _call("fs_critical_emit%dd" % nd, flows.data_ptr(), K, nd, *sp, flows.stride(0) if K > 1 else nd * P, inv_h,
+                  (ctypes.c_double * K)(*ss), vmin, ws.data_ptr(), row_offsets.data_ptr(), N, res["cell"].data_ptr(),
+                  res["simplex"].data_ptr(), res["pos"].data_ptr(), res["jac"].data_ptr(), res["inv"].data_ptr(),
+                  res["cls"].data_ptr(), res["vmax"].data_ptr(), res["status"].data_ptr(), _stream(flows),
+                  algo_bytes=nbytes, algo_flops=flops)
+    return res
+
+
+def critical_points(flows, spacing=1.0, scale=1.0, vmin=0.0):
+    """The critical points of K step flows -- where the field vanishes -- with their kind, two launches
+    (fs_critical_count{2,3}d, fs_critical_emit{2,3}d).
+
+    flows: [K,2,H,W] or [K,3,D,H,W] fp32 displacements on a GPU, in elements, channel 0 along W, every extent >= 2; the
+    step stride may be anything (stack[::2] is read in place).  spacing: the node spacing, one value or one per axis in
+    the tensor's axis order ((D,)H,W).  scale: the reciprocal of the time a step spans, one value or K: velocity =
+    displacement * scale.  vmin: a simplex whose corners all move at most this fast (in elements per step, before
+    `scale`) is quiet and holds no point.
+
+    Every cell is cut into its Kuhn simplices (3-D: the six tetrahedra of ops.isosurface; 2-D: two triangles) and the
+    field taken as affine on each: a simplex holds a point when the signed face minors of its corner values all have one
+    sign, and the point's class follows from the invariants of the affine piece's Jacobian (Routh-Hurwitz: no
+    eigenvalue is computed).  A simplex with a minor that is exactly 0 is reported as degenerate, not resolved.
+    include/flowsci_hip.h states the order of operations; tests/critical_ref.py restates it and agrees bit for bit.
+
+    The number of points depends on the data, so this SYNCHRONISES: exactly once, between the two launches, to learn the
+    steps' offsets (the prefix sum over the rows' counts is torch's).  `status` is therefore returned, not read:
+    ops.critical_points_check(result) reads it.  ValueError when a step has 2^31 - 1 or more points.
+
+    Returns a dict on the device: cell (int32 [N]: the node index of the cell's origin within its step), simplex (uint8
+    [N]: t), pos (fp32 [N,C]: (x, y(, z)) in physical units), jac (fp64 [N,C*C]: d u_r / d x_c at r * C + c), inv (fp64
+    [N,4]: 3-D P, Q, R, Delta of the characteristic polynomial; 2-D tr, det, disc, 0), cls (uint8 [N]: n_pos in bits
+    0-1, CP_SPIRAL, CP_DEGENERATE, CP_MARGINAL; critical_class_names names it), vmax (fp32 [N]: the largest corner speed
+    of the simplex), offsets (int64 [K+1]: step k owns the rows offsets[k] .. offsets[k+1], ordered by cell, then t),
+    counts (int64 [K,4]: points, degenerate simplices, cells with a corner that is not finite, cells with a point) and
+    status (int32 [1]).  Bitwise reproducible.  Nothing is differentiated."""
+    vmin = _cp_vmin(vmin)
+    flows, nd = _advect_flows(flows)
+    sp, P = _lattice(flows.shape[2:])
+    K = int(flows.shape[0])
+    _cp_spacing_scale(spacing, scale, nd, K)
+    ws, off = critical_points_count(flows, vmin)
+    rows = P // sp[-1]
+    R = K * rows
+    steps = off[::rows].contiguous()  # [K+1]
+    host = steps.cpu().numpy()  # the one synchronisation
+    per_step = _np.diff(host)
+    if per_step.size and int(per_step.max()) >= 2 ** 31 - 1:
+        raise ValueError("a step has %d critical points: the limit is 2^31 - 2" % int(per_step.max()))
+    res = critical_points_emit(flows, spacing, scale, vmin, ws, off, int(host[-1]))
+    mask = ws[ws.numel() - K * P:].view(K, P)
+    res["offsets"] = steps
+    res["counts"] = torch.stack([steps[1:] - steps[:-1],
+                                 ws[4 * R:8 * R].view(torch.int32).view(K, rows).sum(1, dtype=torch.int64),
+                                 (mask & CP_MASK_NONFINITE).ne(0).sum(1), (mask & 63).ne(0).sum(1)], 1)
+    return res
+
+
+def critical_points_check(result):
+    """Raises FlowsciKernelError when ops.critical_points' `status` is set (the masks and offsets of its two passes
+    disagreed: the arrays are then not a table).  Synchronises."""
+    st = int(result["status"].view(-1)[0]) if isinstance(result["status"], torch.Tensor) else int(result["status"])
+    if st != 0:
+        raise _lib.FlowsciKernelError("fs_critical_emit: the masks and the row offsets disagree (status %d)" % st)
+
+
+# --------------------------------------------------------------------------------------------
 # Line integral convolution: a texture averaged along the streamlines of step flows (fs_lic{2,3}d)
 # --------------------------------------------------------------------------------------------
 LIC_FULL, LIC_OUT, LIC_STAGNANT, LIC_NONFINITE = 0, 1, 2, 3  # FS_LIC_*: how a side of a line ended
