@@ -63,8 +63,10 @@ enum {
  *   460  fs_lic2d / fs_lic3d and their _ws_bytes queries (line integral convolution: a texture averaged along the
  *        streamlines of step flows).
  *   470  fs_critical_count{2,3}d / fs_critical_emit{2,3}d and their _ws_bytes queries (critical points of step flows:
- *        where the piecewise-linear field vanishes, with its Jacobian, invariants and class). */
-#define FS_ABI_VERSION 470
+ *        where the piecewise-linear field vanishes, with its Jacobian, invariants and class).
+ *   480  fs_streamlines2d / fs_streamlines3d (streamlines of step flows as geometry: every vertex kept, lines ended by
+ *        the border, stagnation, a capturing cell or their length -- what separatrices are traced with). */
+#define FS_ABI_VERSION 480
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -725,7 +727,8 @@ int fs_flow_metrics3d(const float* pred, const float* gt, int N, int C, int D, i
 
 /* ------------------------------------------------------------------------------------
  * The fp64 sample of a step flow -- the one rule by which fs_flow_consistency*, fs_advect* and fs_lic* read a field (or
- * an image or texture plane) at a point and decide whether a point is on the grid (csrc/trilinear64.hpp).  S = (W, H, D)
+ * an image or texture plane) at a point and decide whether a point is on the grid (csrc/trilinear64.hpp); fs_streamlines*
+ * samples by it too.  S = (W, H, D)
  * nodes per axis (2-D: D = 1), points of C components (x, y[, z]) in elements; fp64 without fused multiply-adds:
  *   classify(p): any p_c not finite: non-finite.  Else p_c < 0 or p_c > S_c - 1 for some c: outside (the border is
  *     inclusive; an extent of 1 is legal).  Else on the grid.
@@ -1258,6 +1261,59 @@ int fs_critical_emit3d(const float* flows, int K, int C, int D, int H, int W, lo
                        const double* scale, double vmin, const unsigned char* ws, const long long* row_offsets, long long N,
                        int* cell, unsigned char* simplex, float* pos, double* jac, double* inv, unsigned char* cls,
                        float* vmax, int* status, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Streamlines -- S lines through K steady fields as geometry, one launch: line s starts at its seed and follows the
+ * NORMALISED field of step step[s], with it or against it, for up to M steps of arc length h, and every vertex is kept.
+ *   flows: as for fs_lic*: K fields of C fp32 planes of D*H*W elements (2-D: D = 1, C = 2; 3-D: C = 3), field k at
+ *     + k * flow_sstride elements (flow_sstride >= C*D*H*W when K > 1); channel 0 along W.  Every extent >= 2 and fewer
+ *     than 2^31 nodes.
+ *   seeds: fp64 [C][S], component c at + c * seed_cstride (>= S), in elements, x first.
+ *   step: int32 [S], the field a line runs in.  sign: int8 [S]: a value < 0 runs against the field, anything else with it.
+ *   home: int32 [S] or NULL: the linear index of the cell the line may start in without being captured, or -1 for none.
+ *   capture: uint8 [K][D*H*W], step k at + k * capture_sstride (>= D*H*W when K > 1), or NULL: a nonzero byte at a cell's
+ *     origin node marks a capturing cell.
+ *   M >= 1.  h: the step length in elements, finite and > 0.  vmin: finite and >= 0.
+ *   method: FS_ADV_EULER, FS_ADV_RK2 (midpoint) or FS_ADV_RK4.  h, 0.5 * h and h / 6.0 are formed on the host in fp64;
+ *     the device only negates them.
+ *   verts: fp32; slot i (0 .. M) of line s, component c at i * vert_sstride + c * vert_cstride + s (vert_cstride >= S,
+ *     vert_sstride >= C * vert_cstride).  length: int32 [S].  end: uint8 [S], FS_SL_*.  hit: int32 [S].
+ *   Per line, in fp64 on the widened fp32 values without fused multiply-adds; square root and division are correctly
+ *   rounded; positions stay fp64 for the whole line (a restatement with the same operations in the same order reproduces
+ *   every output bit; tests/streamline_ref.py):
+ *     sample(k, q), classify(p), dir(k, q): those of fs_lic* above -- the clamp, NONFINITE for a sampled component that
+ *       is not finite, n = sqrt((v0*v0 + v1*v1) + v2*v2) (2-D: no third term), STAGNANT for !(n > vmin), d_c = v_c / n.
+ *     Slot 0 receives (float)seed, always.  hit = -1, length = 0, left = (home == NULL or home[s] < 0).
+ *     k = step[s] outside 0 .. K-1: the line ends INVALID.  Else classify(seed) not ALIVE: it ends OUT or NONFINITE.
+ *       Neither samples anything.
+ *     hs = h, hh = 0.5 * h, h6 = h / 6.0, all three negated when sign[s] < 0; p = seed.  For i = 1 .. M:
+ *       d1 = dir(k, p).
+ *       Euler: p' = p + hs * d1.   RK2: d = dir(k, p + hh * d1), p' = p + hs * d.
+ *       RK4: d2 = dir(k, p + hh * d1), d3 = dir(k, p + hh * d2), d4 = dir(k, p + hs * d3),
+ *         p' = p + h6 * (((d1 + 2 * d2) + 2 * d3) + d4).
+ *       A code at any stage ends the line with that code.  Stage points are clamped by sample and never classified.
+ *       classify(p') not ALIVE: the line ends OUT; the exit point is not stored.
+ *       Else p = p', slot i receives (float)p, length = i.
+ *       cell_a = min((int)floor(p_a), S_a - 2), c = (cz * H + cy) * W + cx (the `cell` column of the critical table).
+ *       c != home[s]: left = true.  capture != NULL and left and capture[k][c] != 0: the line ends CAPTURED, hit = c.
+ *     After M steps the line ends FULL.  Slots beyond `length` are not written.
+ *   Every index is formed from a finite value clamped to the grid, and `step` is checked before it selects a field: no
+ *   input makes the kernel read or write outside its operands.  One lane per line; bitwise reproducible.
+ *   FS_ERR_NULLPTR: flows, seeds, step, sign, verts, length, end or hit NULL.  FS_ERR_SHAPE: K < 1, S < 1, C other than 2
+ *   (2-D) / 3 (3-D), an extent < 2, 2^31 nodes or more, a stride below its minimum.  FS_ERR_ARG: M < 1, h not finite or
+ *   <= 0, vmin not finite or < 0, an unknown method.  All of them are returned before anything is launched.
+ */
+enum { FS_SL_FULL = 0, FS_SL_OUT = 1, FS_SL_STAGNANT = 2, FS_SL_NONFINITE = 3, FS_SL_CAPTURED = 4, FS_SL_INVALID = 5 };
+int fs_streamlines2d(const float* flows, int K, int C, int H, int W, long long flow_sstride, const double* seeds,
+                     long long seed_cstride, long long S, const int* step, const signed char* sign, const int* home,
+                     const unsigned char* capture, long long capture_sstride, int M, double h, double vmin, int method,
+                     float* verts, long long vert_sstride, long long vert_cstride, int* length, unsigned char* end,
+                     int* hit, fs_stream_t stream);
+int fs_streamlines3d(const float* flows, int K, int C, int D, int H, int W, long long flow_sstride, const double* seeds,
+                     long long seed_cstride, long long S, const int* step, const signed char* sign, const int* home,
+                     const unsigned char* capture, long long capture_sstride, int M, double h, double vmin, int method,
+                     float* verts, long long vert_sstride, long long vert_cstride, int* length, unsigned char* end,
+                     int* hit, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

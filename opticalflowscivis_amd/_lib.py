@@ -33,7 +33,7 @@ def switches():
     return {"library": "ablation build: " + LIB_PATH if ABLATION else "product",
             "env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("FLOWSCI_")}}
 
-ABI_VERSION = 470  # FS_ABI_VERSION of the include/flowsci_hip.h the SIGNATURES below were written against
+ABI_VERSION = 480  # FS_ABI_VERSION of the include/flowsci_hip.h the SIGNATURES below were written against
 
 _f32p = ctypes.c_void_p  # device pointers travel as integers
 _int = ctypes.c_int
@@ -188,6 +188,10 @@ SIGNATURES = {
     "fs_critical_count3d": [_f32p] + [_int] * 5 + [_i64, _double, _f32p, _stream],
     "fs_critical_emit2d": [_f32p] + [_int] * 4 + [_i64, _f64p, _f64p, _double, _f32p, _f32p, _i64] + [_f32p] * 8 + [_stream],
     "fs_critical_emit3d": [_f32p] + [_int] * 5 + [_i64, _f64p, _f64p, _double, _f32p, _f32p, _i64] + [_f32p] * 8 + [_stream],
+    "fs_streamlines2d": [_f32p, _int, _int, _int, _int, _i64, _f32p, _i64, _i64] + [_f32p] * 4 + [_i64, _int, _double, _double, _int,
+                         _f32p, _i64, _i64] + [_f32p] * 3 + [_stream],
+    "fs_streamlines3d": [_f32p, _int, _int, _int, _int, _int, _i64, _f32p, _i64, _i64] + [_f32p] * 4 + [_i64, _int, _double, _double,
+                         _int, _f32p, _i64, _i64] + [_f32p] * 3 + [_stream],
     "fs_triplet_gather": [_f32p, _int, _i64, _int, _int, _int, _f32p, _int, _int, _int, _int, _f32p, _stream],
     "fs_series_stats_ws_bytes": [_int, _i64],
     "fs_series_stats": [_f32p, _int, _int, _i64, _f32p, _f32p, _stream],

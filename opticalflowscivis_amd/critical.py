@@ -14,7 +14,9 @@ the zeros of `--chunk` steps in two launches; the per-step tables stay on the ho
 equal n_pos within --link-radius) are plumbing.  --out holds every column of the table, `offsets`, `track` and `frames`;
 --json the per-step rows; --png-dir (2-D) one picture per step with a marker per point, coloured by class.
 
-Out of scope: separatrices and full topological skeletons; higher-order critical points and those of the trilinear
+The lines that leave the saddles -- the separatrices -- are skeleton.py's, which starts from this table.
+
+Out of scope: higher-order critical points and those of the trilinear
 interpolant of a cell; simulation-of-simplicity handling of exact ties (a simplex with a face minor of exactly 0 is
 reported as `degenerate`, not resolved); periodic domains; tracking through space-time cells (steps are linked by
 distance); autograd through the op."""
@@ -119,12 +121,14 @@ def parse_classes(text, nd):
 
 
 def critical_series(step_flows, n_steps, sp, spacing=1.0, vmin=0.0, chunk=4, frames=None, dt=1.0, min_jnorm=0.0,
-                    classes=None, link_radius=0.0):
+                    classes=None, link_radius=0.0, on_chunk=None):
     """The critical points of the n_steps step flows that step_flows(j0, j1) -> [j1 - j0, C, *sp] hands out `chunk` at a
     time (each exactly once, one ops.critical_points call per chunk).  frames: the n_steps + 1 frames the chain visits
     (default 0..n_steps); a step's velocities are its displacements / (frames spanned * dt).  Filters, applied on the
     host to every column alike: min_jnorm (the Frobenius norm of the Jacobian) and classes (a set of
-    ops.critical_class_names names, None for all); vmin goes to the kernel.  link_radius: see link_points.
+    ops.critical_class_names names, None for all); vmin goes to the kernel.  link_radius: see link_points.  on_chunk:
+    called as on_chunk(j0, j1, flows, tables[j0:j1]) once per chunk while its flows are still on the device (skeleton.py
+    traces its lines there: the flows are estimated once).
 
     Returns a dict: tables (one dict of host arrays per step: cell, simplex, pos, jac, inv, cls, vmax), track (one int64
     array per step), steps (one dict per step: step, t_from, t_to, scale, n_found -- what the kernel found --, n_points
@@ -177,6 +181,8 @@ def critical_series(step_flows, n_steps, sp, spacing=1.0, vmin=0.0, chunk=4, fra
                            degenerate_simplices=int(counts[j - j0, 1]), nonfinite_cells=int(counts[j - j0, 2]),
                            index_sum=int(np.nan_to_num(sign).sum()))
             tables.append(tab)
+        if on_chunk is not None:
+            on_chunk(j0, j1, f, tables[j0:j1])
         del f, r
     track, births, deaths = link_points(tables, link_radius)
     for j, row in enumerate(rows):
@@ -200,13 +206,15 @@ def table_arrays(res, nd, frames):
     return out
 
 
-def draw_points(grey, tab, spacing):
+def draw_points(grey, tab, spacing, img=None):
     """An RGB uint8 picture [H, W, 3]: `grey` ([H, W] in [0, 1]) with a plus-shaped marker at every
     point of the 2-D table `tab`, coloured by n_pos (sink blue, saddle green, source red; a focus lighter; anything
-    degenerate or a center white)."""
+    degenerate or a center white).  img: an RGB uint8 picture [H, W, 3] to draw the markers into instead (it is returned;
+    `grey` then only gives the extent)."""
     from . import render
     H, W = grey.shape
-    img = np.repeat(render.to_uint8(grey)[:, :, None], 3, axis=2)
+    if img is None:
+        img = np.repeat(render.to_uint8(grey)[:, :, None], 3, axis=2)
     hy, hx = spacing
     for (x, y), c in zip(tab["pos"], tab["cls"]):
         c = int(c)

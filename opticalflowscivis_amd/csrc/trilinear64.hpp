@@ -1,7 +1,7 @@
 // trilinear64.hpp -- the fp64 trilinear (bilinear in 2-D) sample of a step flow and the classification of a point
 // against the grid: the statement of the rule that flowconsist.hip, advect.hip and lic.hip follow and that two
-// independent numpy restatements pin bit for bit (tests/flow_consistency_ref.py, tests/advect_ref.py).  Only lic.hip
-// includes this header.  flowconsist.hip, where the rule was first written, and advect.hip keep their own copies of the
+// independent numpy restatements pin bit for bit (tests/flow_consistency_ref.py, tests/advect_ref.py).  lic.hip and
+// streamline.hip include this header.  flowconsist.hip, where the rule was first written, and advect.hip keep their own copies of the
 // same lines, because kernels of theirs measured slower on the header than the parent's spread allows
 // (profiles/trilinear64.txt): a change to the rule is made here AND in those two files.  A later step-flow tool starts
 // from here.

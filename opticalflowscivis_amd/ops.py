@@ -4035,6 +4035,122 @@ def lic(flows, tex, length=16, h=0.5, method="rk2", kernel="box", vmin=0.0, with
 
 
 # --------------------------------------------------------------------------------------------
+# Streamlines: lines through step flows kept as geometry (fs_streamlines{2,3}d)
+# --------------------------------------------------------------------------------------------
+SL_FULL, SL_OUT, SL_STAGNANT, SL_NONFINITE, SL_CAPTURED, SL_INVALID = 0, 1, 2, 3, 4, 5  # FS_SL_*: how a line ended
+streamline_end_names = ("full", "out", "stagnant", "nonfinite", "captured", "invalid")  # by FS_SL_* code
+
+
+def _sl_steps(M):
+    if isinstance(M, bool) or int(M) != M or int(M) < 1:
+        raise ValueError("max_steps must be an integer >= 1, got %r" % (M,))
+    return int(M)
+
+
+def streamlines_cost(shape, S, M, method="rk4"):
+    """(HBM bytes, flops) the algorithm needs for one streamlines call of S lines of M steps on fields of spatial
+    `shape`, every line at full length: every field element the gathers can reach read once (at most what the
+    S * M * stages samples of 2^C corners x C planes ask for; the fields a call does not visit are not known here, so no
+    whole-field cap applies), seeds (8 C), step, sign and home (9) read, the M + 1 slots (4 C each), length, end and hit
+    (9) written, one capture byte read per step.  Flops per sample as in lic_cost: the field sample of advect_cost plus
+    2 C for n2 and its root, C divisions and 2 C for the stage point; ~4 C per step for the update, its classification
+    and the cell (RK4: 5 C more for the stage sum)."""
+    if method not in _ADV_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(_ADV_METHODS), method))
+    M = _sl_steps(M)
+    shape = tuple(int(s) for s in shape)
+    C = len(shape)
+    if C not in (2, 3) or min(shape) < 2:
+        raise ValueError("shape must be (H,W) or (D,H,W) with every extent >= 2, got %r" % (shape,))
+    S = int(S)
+    if S < 0:
+        raise ValueError("S must be >= 0, got %d" % S)
+    stages = _ADV_METHODS[method][1]
+    samples = S * M * stages
+    corners = 1 << C
+    nbytes = 4 * samples * corners * C + S * (8 * C + 9 + 4 * C * (M + 1) + 9 + M)
+    per_sample = corners * (C - 1) + 2 * corners * C + 4 * C + 3 * C + 2 * C
+    return nbytes, samples * per_sample + S * M * (4 * C + (5 * C if method == "rk4" else 0))
+
+
+def streamlines(flows, seeds, step, sign, home=None, capture=None, max_steps=256, h=0.5, vmin=0.0, method="rk4"):
+    """Streamlines of steady step flows as geometry, one launch (fs_streamlines{2,3}d): line s starts at seeds[s] and
+    follows the NORMALISED field flows[step[s]] -- with it, or against it where sign[s] < 0 -- for up to `max_steps`
+    steps of `h` elements of arc length; every vertex is kept.
+
+    flows: [K,2,H,W] or [K,3,D,H,W] fp32 on a GPU (channel 0 along W), every extent >= 2; the step stride may be
+    anything.  seeds: fp64 [S,C] on the flows' device, (x, y(, z)) in elements.  step: int32 [S].  sign: int8 [S].
+    home: int32 [S] or None: the cell (its origin node's linear index within the step) a line may start in without being
+    captured there, -1 for none.  capture: uint8 [K,*sp] or None: a nonzero byte at a cell's origin node ends a line that
+    steps into that cell (CAPTURED) once it has left its home.  method: "euler", "rk2" (midpoint) or "rk4" on the unit
+    direction field.  vmin: a line ends STAGNANT where the speed is not above vmin.
+
+    All arithmetic is fp64 and positions stay fp64 for the whole line (include/flowsci_hip.h states the order of
+    operations; tests/streamline_ref.py restates it and agrees bit for bit).  A line also ends where the next point
+    would leave the grid (OUT: the border is inside, the exit point is not stored), where the field is not finite
+    (NONFINITE) or after max_steps (FULL); a seed outside the grid (OUT), a seed that is not finite (NONFINITE) and a
+    step outside 0..K-1 (INVALID) end a line of length 0.
+
+    Returns a dict on the device: verts fp32 [max_steps+1, C, S] (allocated uninitialised: of line s only
+    verts[0 .. length[s], :, s] are defined; slot 0 is the seed), length int32 [S], end uint8 [S] (SL_*; names in
+    streamline_end_names), hit int32 [S] (the capturing cell, else -1).  Never synchronises.  A measurement on detached
+    values: nothing is differentiated."""
+    if method not in _ADV_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(_ADV_METHODS), method))
+    M = _sl_steps(max_steps)
+    h, vmin = float(h), float(vmin)
+    if not (0.0 < h < float("inf")):
+        raise ValueError("h must be finite and > 0, got %r" % (h,))
+    if not (0.0 <= vmin < float("inf")):
+        raise ValueError("vmin must be finite and >= 0, got %r" % (vmin,))
+    flows, nd = _advect_flows(flows)
+    dev = flows.device
+    K = int(flows.shape[0])
+    sp = tuple(int(s) for s in flows.shape[2:])
+    if min(sp) < 2:
+        raise ValueError("every extent of flows must be >= 2, got %s" % (sp,))
+    plane = 1
+    for v in sp:
+        plane *= v
+
+    def operand(name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a tensor" % name)
+        if not t.is_cuda:
+            raise ValueError("%s must live on a GPU (the HIP hot path has no CPU fallback); got %s" % (name, t.device))
+        if t.device != dev:
+            raise ValueError("%s must be on the flows' device %s, got %s" % (name, dev, t.device))
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError("%s must be a %s tensor of shape %s, got %s %s" % (name, dtype, shape, t.dtype, tuple(t.shape)))
+        return t.detach().contiguous()
+
+    if not isinstance(seeds, torch.Tensor) or seeds.dim() != 2 or seeds.shape[1] != nd:
+        raise ValueError("seeds must be an fp64 tensor [S,%d] for %d-D flows, got %s" %
+                         (nd, nd, tuple(seeds.shape) if isinstance(seeds, torch.Tensor) else type(seeds).__name__))
+    S = int(seeds.shape[0])
+    seeds = operand("seeds", seeds, torch.float64, (S, nd))
+    step = operand("step", step, torch.int32, (S,))
+    sign = operand("sign", sign, torch.int8, (S,))
+    home = None if home is None else operand("home", home, torch.int32, (S,))
+    capture = None if capture is None else operand("capture", capture, torch.uint8, (K,) + sp)
+    res = {"verts": torch.empty((M + 1, nd, S), dtype=torch.float32, device=dev),
+           "length": torch.empty(S, dtype=torch.int32, device=dev), "end": torch.empty(S, dtype=torch.uint8, device=dev),
+           "hit": torch.empty(S, dtype=torch.int32, device=dev)}
+    if S == 0:
+        return res
+    sc = seeds.t().contiguous()  # [C,S]: a wave's loads of a component are coalesced
+    fss = flows.stride(0) if K > 1 else nd * plane  # (a single field's step stride is never used)
+    nbytes, flops = streamlines_cost(sp, S, M, method)
+    args = (flows.data_ptr(), K, nd) + sp + (fss, sc.data_ptr(), S, S, step.data_ptr(), sign.data_ptr(), _ptr(home),
+                                             _ptr(capture), plane, M, h, vmin, _ADV_METHODS[method][0],
+                                             res["verts"].data_ptr(), nd * S, S, res["length"].data_ptr(),
+                                             res["end"].data_ptr(), res["hit"].data_ptr(), _stream(flows))
+    with torch.cuda.device(dev):
+        _call("fs_streamlines%dd" % nd, *args, algo_bytes=nbytes, algo_flops=flops)
+    return res
+
+
+# --------------------------------------------------------------------------------------------
 # Training batches out of a device-resident stored series (fs_triplet_gather, fs_series_stats)
 # --------------------------------------------------------------------------------------------
 import numpy as _np
