@@ -65,8 +65,10 @@ enum {
  *   470  fs_critical_count{2,3}d / fs_critical_emit{2,3}d and their _ws_bytes queries (critical points of step flows:
  *        where the piecewise-linear field vanishes, with its Jacobian, invariants and class).
  *   480  fs_streamlines2d / fs_streamlines3d (streamlines of step flows as geometry: every vertex kept, lines ended by
- *        the border, stagnation, a capturing cell or their length -- what separatrices are traced with). */
-#define FS_ABI_VERSION 480
+ *        the border, stagnation, a capturing cell or their length -- what separatrices are traced with).
+ *   490  fs_pv_count3d / fs_pv_emit3d / fs_pv3d_ws_bytes (parallel vectors: the segments of the locus v || w on the Kuhn
+ *        split -- vortex core lines after Sujudi-Haimes (w = J v) and Levy et al. (w = vorticity)). */
+#define FS_ABI_VERSION 490
 int fs_version(void);
 /* Static string for an FS_* code. */
 const char* fs_error_string(int code);
@@ -1314,6 +1316,104 @@ int fs_streamlines3d(const float* flows, int K, int C, int D, int H, int W, long
                      const unsigned char* capture, long long capture_sstride, int M, double h, double vmin, int method,
                      float* verts, long long vert_sstride, long long vert_cstride, int* length, unsigned char* end,
                      int* hit, fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Parallel vectors -- the line-type feature that goes with the vortex regions: the locus where two vector fields v and w
+ * of K steps are parallel (Peikert and Roth), as line segments, one per tetrahedron of the Kuhn split that the locus
+ * crosses.  w = J v gives the vortex core lines of Sujudi and Haimes, w = vorticity those of Levy et al.  3-D only: in
+ * 2-D the locus is a curve, not a feature.  Two passes with the caller's prefix sum between them, shaped like the
+ * critical-point pair.
+ *   v, w: K fields each of 3 fp32 planes of D*H*W elements, field k at + k * v_sstride (w_sstride) elements (>= 3*D*H*W:
+ *     every other field of a stack is read in place), node (z, y, x) at (z * H + y) * W + x; component 0 and axis 0 run
+ *     along x (W), 1 along y, 2 along z.  Every extent >= 2.
+ *   aux: NULL, or fp32 [K][D*H*W], step k at + k * aux_sstride (>= D*H*W): a scalar carried along to the points.
+ *   inv_h: HOST array of 3 doubles, 1 / h_a, finite and positive; it travels in the launch's arguments.
+ *   vmin, wmin: >= 0, finite, rounded to fp32 once.
+ *   All arithmetic below is fp64 on the widened fp32 values, without fused multiply-adds, in exactly the written order,
+ *   with + - * / sqrt (correctly rounded) and comparisons only: a restatement with the same operations in the same
+ *   order reproduces every bit (tests/pv_ref.py).
+ *   Simplices.  The six tetrahedra t = 0..5 of the critical-point section: corners 0, c1(t), c2(t), 7 of the cell, with
+ *     c1 = 1 1 2 2 4 4 and c2 = 3 5 3 6 5 6.  Face f of a tetrahedron is the triangle that omits its corner f; its three
+ *     corners stay in increasing node index.
+ *   Faces.  Every face is OWNED by the node that is its lowest corner and lives in one of that node's 12 slots: slot s
+ *     has the corners 0 < mid(s) < hi(s) of the cell the node is the origin of (corner c at the offset
+ *     (dz, dy, dx) = (c >> 2 & 1, c >> 1 & 1, c & 1)):
+ *         s     0  1  2  3  4  5  6  7  8  9 10 11
+ *         mid   1  1  2  2  4  4  3  5  6  1  2  4
+ *         hi    3  5  3  6  5  6  7  7  7  7  7  7
+ *     A node owns slot s when all three corners are nodes of the grid (nodes of the far borders own the slots that lie in
+ *     the border).  The global face id is (owner's node index within the step) * 12 + s.  Face f of tetrahedron t of a
+ *     cell is owned by the cell's corner o(t, f), in slot s(t, f):
+ *         f = 0: o = c1(t), s = 3 5 1 4 0 2 (t = 0..5)      f = 1: o = 0, s = 6 7 6 8 7 8
+ *         f = 2: o = 0,     s = 9 + (t >> 1)                f = 3: o = 0, s = t
+ *     A face is evaluated in its OWNER's frame only -- origin (ox, oy, oz) = the owner, corners 0, mid, hi, values
+ *     v_i, w_i, aux_i (i = 0..2) -- so the two tetrahedra that share it, in one cell or across cells, see the same
+ *     expressions on the same nodes in the same order: where both emit a segment that ends on the face, key, pos, mu,
+ *     vel and aux are the same bits.  Everything downstream (linking segments into lines) rests on this.
+ *   Per face.  A face with a corner at which a component of v or w, or aux when given, is not finite holds nothing and
+ *     is not counted.  Otherwise:
+ *     1. Quiet.  Corner i is quiet when (vx^2 + vy^2) + vz^2 <= ((double)(float)vmin)^2 or the same sum of w_i <=
+ *        ((double)(float)wmin)^2.  A face whose three corners are all quiet holds nothing.
+ *     2. Reject.  For every component k of the cross product, with (j, l) = (1, 2), (2, 0), (0, 1) for k = 0, 1, 2 and
+ *        x(p, q) = v_p[j] * w_q[l] - v_p[l] * w_q[j]:  the six numbers x(0,0), x(1,1), x(2,2), x(0,1) + x(1,0),
+ *        x(0,2) + x(2,0), x(1,2) + x(2,1) are, up to a factor, the Bernstein coefficients of (v x w)_k on the face.  If for
+ *        some k all six are > 0 or all six are < 0, the face holds nothing.  (Rigorous: it removes no point.)
+ *     3. Pencil.  det3 as in the critical-point section.  dV = det3(v0, v1, v2), dW = det3(w0, w1, w2).  A = w, B = v when
+ *        |dW| >= |dV|; otherwise A = v, B = w ("swapped").  dA equal to 0 or not finite: the face is DEGENERATE, it is
+ *        counted and holds nothing.  m1 = (det3(A0,B1,B2) + det3(B0,A1,B2)) + det3(B0,B1,A2),
+ *        m2 = (det3(A0,A1,B2) + det3(A0,B1,A2)) + det3(B0,A1,A2);  a = -(m2 / dA), b = m1 / dA, c = -(dB / dA);
+ *        p(x) = ((x + a) * x + b) * x + c, the monic det(B - x A) / -dA;  p'(x) = (3 * x + 2 * a) * x + b.
+ *     4. Real roots.  R = 1 + max(|a|, |b|, |c|) (the maximum by > from the left);  disc = a * a - 3 * b.
+ *        disc > 0: q = sqrt(disc), k1 = (-a - q) / 3, k2 = (-a + q) / 3; otherwise k1 = k2 = -R.
+ *        For the intervals (lo, hi) = (-R, k1), (k1, k2), (k2, R) in this order: when lo < hi and (p(lo) < 0) differs from
+ *        (p(hi) < 0), the interval holds one root: 64 times m = 0.5 * (lo + hi), then lo = m when (p(m) < 0) equals what
+ *        (p(lo) < 0) was at the start, else hi = m;  x = 0.5 * (lo + hi);  then twice x' = x - p(x) / p'(x), taken
+ *        (x = x') only when x' is finite and lo <= x' <= hi.  The roots of a face are ranked r = 0, 1, 2 in this order.
+ *     5. Per root x.  N[c][i] = B_i[c] - x * A_i[c] (rows c: components, columns i: corners).  n = the cross product
+ *        (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0) of the row pair (0,1), (0,2) or (1,2) with the largest
+ *        (n0^2 + n1^2) + n2^2; a later pair wins only when strictly larger.  The root is an accepted POINT when n0, n1,
+ *        n2 are all > 0 or all < 0.  S = (n0 + n1) + n2, l_i = n_i / S.
+ *        Coordinate along axis a: c = (double)o_a;  c = c + l_1 when bit a of mid is set;  c = c + l_2 when bit a of hi
+ *        is set;  pos[a] = (float)(c / inv_h[a]), stored (x, y, z).
+ *        mu (w = mu * v at the point) = x when swapped, else 1 / x; it may be +-inf or 0.
+ *        vel[c] = (float)((l_0 * v_0[c] + l_1 * v_1[c]) + l_2 * v_2[c]);  aux likewise.
+ *        key = 4 * (global face id) + r.
+ *   Per cell.  A cell is a node whose coordinates are all below extent - 1.  A cell with a corner at which a component
+ *     of v or w, or aux when given, is not finite is NONFINITE: none of its tetrahedra counts or emits anything.
+ *   Per tetrahedron.  n = the points of its four faces.  n == 2: one segment, its endpoints in (f, r) order.  n == 0:
+ *     nothing.  Anything else: AMBIGUOUS; it is counted and emits nothing (pairing four points is a choice).
+ *   The segments of a step are ordered by cell index, then by t.  Bitwise reproducible: no atomic decides a value or an
+ *   order.
+ *
+ * fs_pv_count3d -- all K steps; two kernels on the stream (faces by their owners, then tetrahedra).  ws: fs_pv3d_ws_bytes
+ *     bytes, 16-byte aligned, written as  int32 nseg[R], namb[R], ndeg[R], nnf[R] with R = K*D*H: per row (k, z, y) the
+ *     segments and the ambiguous tetrahedra of its cells, the degenerate faces its nodes own (each face once) and its
+ *     nonfinite cells; padding to a multiple of 16 bytes;  uint32 faces[K][D*H*W]: bits 2s, 2s+1 = the points of the
+ *     node's slot s, FS_PV_NODE_NONFINITE = a value at the node is not finite;  uint8 mask[K][D*H*W], one byte per
+ *     cell's origin node: bit t = tetrahedron t holds a segment, FS_PV_MASK_AMBIGUOUS, FS_PV_MASK_NONFINITE.
+ * The caller turns nseg into row_offsets, int64 [R + 1] in DEVICE memory: the exclusive prefix sum with N at the end.
+ * fs_pv_emit3d -- one launch (none when N = 0) on the same operands.  It re-solves, in the owner's frame, those faces of
+ *   the flagged tetrahedra whose count is not 0.  Segment = row (row offset + in-row prefix + rank of t in the cell's
+ *   mask) of cell int32 [N] (the cell's node index within its step), simplex uint8 [N], face uint8 [N][2] (f of each
+ *   endpoint), key int64 [N][2], pos fp32 [N][2][3], mu fp64 [N][2], vel fp32 [N][2][3] and, when aux is given, aux_out
+ *   fp32 [N][2].  Nothing is written at or beyond row N.  status: int32 [1], zeroed by the CALLER; bit 0 is set when the
+ *   passes disagree (the mask, the offsets, or a re-solved face) -- the outputs are then not a table.
+ *   FS_ERR_NULLPTR: v, w, ws (inv_h, row_offsets, status) NULL; an output with N > 0 (aux_out only when aux is given).
+ *   FS_ERR_SHAPE: K < 1 or K*D*H above 2^31 - 1, an extent below 2, 2^31 - 1 nodes or more, v_sstride or w_sstride
+ *   below 3*D*H*W, aux_sstride below D*H*W when aux is given.  FS_ERR_ARG: vmin or wmin negative or not finite (as fp32),
+ *   an inv_h[a] that is not finite or not positive, N negative, ws not 16-byte aligned.  All of them are returned before
+ *   anything is launched; the _ws_bytes query launches nothing and returns the byte count or -(FS_ERR_*).
+ */
+enum { FS_PV_MASK_AMBIGUOUS = 64, FS_PV_MASK_NONFINITE = 128, FS_PV_NODE_NONFINITE = 1 << 24 };
+long long fs_pv3d_ws_bytes(int K, int D, int H, int W);
+int fs_pv_count3d(const float* v, long long v_sstride, const float* w, long long w_sstride, const float* aux,
+                  long long aux_sstride, int K, int D, int H, int W, double vmin, double wmin, unsigned char* ws,
+                  fs_stream_t stream);
+int fs_pv_emit3d(const float* v, long long v_sstride, const float* w, long long w_sstride, const float* aux,
+                 long long aux_sstride, int K, int D, int H, int W, const double* inv_h, double vmin, double wmin,
+                 const unsigned char* ws, const long long* row_offsets, long long N, int* cell, unsigned char* simplex,
+                 unsigned char* face, long long* key, float* pos, double* mu, float* vel, float* aux_out, int* status,
+                 fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

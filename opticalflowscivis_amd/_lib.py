@@ -33,7 +33,7 @@ def switches():
     return {"library": "ablation build: " + LIB_PATH if ABLATION else "product",
             "env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("FLOWSCI_")}}
 
-ABI_VERSION = 480  # FS_ABI_VERSION of the include/flowsci_hip.h the SIGNATURES below were written against
+ABI_VERSION = 490  # FS_ABI_VERSION of the include/flowsci_hip.h the SIGNATURES below were written against
 
 _f32p = ctypes.c_void_p  # device pointers travel as integers
 _int = ctypes.c_int
@@ -192,6 +192,10 @@ SIGNATURES = {
                          _f32p, _i64, _i64] + [_f32p] * 3 + [_stream],
     "fs_streamlines3d": [_f32p, _int, _int, _int, _int, _int, _i64, _f32p, _i64, _i64] + [_f32p] * 4 + [_i64, _int, _double, _double,
                          _int, _f32p, _i64, _i64] + [_f32p] * 3 + [_stream],
+    "fs_pv3d_ws_bytes": [_int] * 4,
+    "fs_pv_count3d": [_f32p, _i64, _f32p, _i64, _f32p, _i64] + [_int] * 4 + [_double, _double, _f32p, _stream],
+    "fs_pv_emit3d": [_f32p, _i64, _f32p, _i64, _f32p, _i64] + [_int] * 4 + [_f64p, _double, _double, _f32p, _f32p, _i64] +
+                    [_f32p] * 9 + [_stream],
     "fs_triplet_gather": [_f32p, _int, _i64, _int, _int, _int, _f32p, _int, _int, _int, _int, _f32p, _stream],
     "fs_series_stats_ws_bytes": [_int, _i64],
     "fs_series_stats": [_f32p, _int, _int, _i64, _f32p, _f32p, _stream],
@@ -213,6 +217,7 @@ _RESTYPES = {"fs_error_string": ctypes.c_char_p, "fs_conv3d_fwd_ws_floats": ctyp
              "fs_raycast3d_ws_bytes": ctypes.c_longlong, "fs_iso3d_ws_bytes": ctypes.c_longlong,
              "fs_lic2d_ws_bytes": ctypes.c_longlong, "fs_lic3d_ws_bytes": ctypes.c_longlong,
              "fs_critical2d_ws_bytes": ctypes.c_longlong, "fs_critical3d_ws_bytes": ctypes.c_longlong,
+             "fs_pv3d_ws_bytes": ctypes.c_longlong,
              "fs_series_stats_ws_bytes": ctypes.c_longlong, "fs_series_encode_ws_bytes": ctypes.c_longlong,
              "fs_conv3d_tr_ws_floats": ctypes.c_longlong, "fs_conv3d_fwd_dprelu_part_floats": ctypes.c_longlong,
              "fs_conv3d_fwd_dprelu_part_floats_k3": ctypes.c_longlong}

@@ -3893,6 +3893,172 @@ def critical_points_check(result):
 
 
 # --------------------------------------------------------------------------------------------
+# Parallel vectors: the segments of the locus v || w -- vortex core lines (fs_pv_count3d, fs_pv_emit3d)
+# --------------------------------------------------------------------------------------------
+PV_MASK_AMBIGUOUS, PV_MASK_NONFINITE, PV_NODE_NONFINITE = 64, 128, 1 << 24  # FS_PV_*
+PV_COLUMNS = ("cell", "simplex", "face", "key", "pos", "mu", "vel")          # and "aux" when one is carried along
+
+
+def parallel_vectors_cost(shape, K=1, N=0, op="count", aux=False):
+    """(HBM bytes, flops) the algorithm needs for one pass of ops.parallel_vectors over K steps of spatial `shape`
+    (D,H,W).  "count": the 6 (7 with aux) values of every node read once, its face word written and read (4 + 4), its
+    mask byte written, four int32 per row; ~1100 fp64 flops of screening per node (12 faces: 18 cross-product
+    coefficients each).  "emit": the mask bytes read and the N rows written (4 cell + 1 simplex + 2 face + 16 key + 24 pos
+    + 16 mu + 24 vel (+ 8 aux)); flops: ~2000 per re-solved endpoint.  The solves of surviving faces depend on the field
+    and are on top."""
+    sp, P = _lattice(shape)
+    K, N = int(K), int(N)
+    if len(sp) != 3 or K < 1 or N < 0:
+        raise ValueError("a (D,H,W) shape, K >= 1 and N >= 0, got %r, %d, %d" % (shape, K, N))
+    rows = P // sp[-1]
+    if op == "count":
+        return K * (P * (4 * (7 if aux else 6) + 8 + 1) + 16 * rows), K * P * 1100
+    if op == "emit":
+        return K * P + N * (87 + (8 if aux else 0)), N * 4000
+    raise ValueError("op must be 'count' or 'emit', got %r" % (op,))
+
+
+def _pv_operands(v, w, aux):
+    v, nd = _advect_flows(v)
+    if nd != 3:
+        raise ValueError("parallel vectors are 3-D only ([K,3,D,H,W]), got shape %s" % (tuple(v.shape),))
+    if not isinstance(w, torch.Tensor) or tuple(w.shape) != tuple(v.shape) or w.device != v.device:
+        raise ValueError("w must be a tensor of v's shape %s on v's device" % (tuple(v.shape),))
+    w = _flow_operand("w", w.detach(), 3)
+    K = int(v.shape[0])
+    if aux is not None:
+        if not isinstance(aux, torch.Tensor) or tuple(aux.shape) != (K,) + tuple(v.shape[2:]) or aux.device != v.device:
+            raise ValueError("aux must be a tensor [K,D,H,W] = %s on v's device" % ((K,) + tuple(v.shape[2:]),))
+        aux = aux.detach().to(torch.float32)
+        if not aux[0].is_contiguous() or (K > 1 and aux.stride(0) < aux[0].numel()):
+            aux = aux.contiguous()
+    return v, w, aux
+
+
+def _pv_field_args(v, w, aux, K, P):
+    return (v.data_ptr(), v.stride(0) if K > 1 else 3 * P, w.data_ptr(), w.stride(0) if K > 1 else 3 * P, _ptr(aux),
+            (aux.stride(0) if K > 1 else P) if aux is not None else 0)
+
+
+def _pv_min(name, m):
+    try:
+        m = float(m)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number, got %r" % (name, m))
+    if not 0 <= m < float("inf"):
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, m))
+    return m
+
+
+def parallel_vectors_count(v, w, aux=None, vmin=0.0, wmin=0.0):
+    """The first pass of ops.parallel_vectors on its own (fs_pv_count3d): the workspace (uint8: four int32 counts per
+    row, one uint32 of face counts per node, one mask byte per node) and row_offsets, int64 [K*D*H + 1] on the device:
+    the exclusive prefix sum of the rows' segment counts (plumbing: torch.cumsum).  Never synchronises."""
+    vmin, wmin = _pv_min("vmin", vmin), _pv_min("wmin", wmin)
+    v, w, aux = _pv_operands(v, w, aux)
+    sp, P = _lattice(v.shape[2:])
+    K = int(v.shape[0])
+    dev = v.device
+    R = K * (P // sp[-1])
+    nb = _lib.lib().fs_pv3d_ws_bytes(K, *sp)
+    if nb < 0:
+        _lib.check(int(-nb), "fs_pv3d_ws_bytes")
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    nbytes, flops = parallel_vectors_cost(sp, K, op="count", aux=aux is not None)
+    with torch.cuda.device(dev):
+        _call("fs_pv_count3d", *_pv_field_args(v, w, aux, K, P), K, *sp, vmin, wmin, ws.data_ptr(), _stream(v),
+              algo_bytes=nbytes, algo_flops=flops)
+    off = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(ws[:4 * R].view(torch.int32), 0, dtype=torch.int64)
+    return ws, off
+
+
+def parallel_vectors_emit(v, w, aux, spacing, vmin, wmin, ws, row_offsets, N):
+    """The second pass of ops.parallel_vectors on its own (fs_pv_emit3d), on what parallel_vectors_count returned and
+    the total N as a host int.  Returns a dict on the device: cell, simplex, face, key, pos, mu, vel, (aux,) status.
+    Never synchronises; launches nothing when N is 0."""
+    vmin, wmin = _pv_min("vmin", vmin), _pv_min("wmin", wmin)
+    v, w, aux = _pv_operands(v, w, aux)
+    sp, P = _lattice(v.shape[2:])
+    K = int(v.shape[0])
+    hs, _ = _cp_spacing_scale(spacing, 1.0, 3, K)
+    dev = v.device
+    N = int(N)
+    if N < 0:
+        raise ValueError("N must be >= 0, got %d" % N)
+    res = {"cell": torch.empty(N, dtype=torch.int32, device=dev), "simplex": torch.empty(N, dtype=torch.uint8, device=dev),
+           "face": torch.empty((N, 2), dtype=torch.uint8, device=dev), "key": torch.empty((N, 2), dtype=torch.int64, device=dev),
+           "pos": torch.empty((N, 2, 3), dtype=torch.float32, device=dev),
+           "mu": torch.empty((N, 2), dtype=torch.float64, device=dev),
+           "vel": torch.empty((N, 2, 3), dtype=torch.float32, device=dev)}
+    if aux is not None:
+        res["aux"] = torch.empty((N, 2), dtype=torch.float32, device=dev)
+    res["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    if N:
+        nbytes, flops = parallel_vectors_cost(sp, K, N, op="emit", aux=aux is not None)
+        # component 0 and axis 0 run along x: the tensor's last axis
+        inv_h = (ctypes.c_double * 3)(*[1.0 / h for h in hs[::-1]])
+        with torch.cuda.device(dev):
+            _call("fs_pv_emit3d", *_pv_field_args(v, w, aux, K, P), K, *sp, inv_h, vmin, wmin, ws.data_ptr(),
+                  row_offsets.data_ptr(), N, res["cell"].data_ptr(), res["simplex"].data_ptr(), res["face"].data_ptr(),
+                  res["key"].data_ptr(), res["pos"].data_ptr(), res["mu"].data_ptr(), res["vel"].data_ptr(),
+                  _ptr(res.get("aux")), res["status"].data_ptr(), _stream(v), algo_bytes=nbytes, algo_flops=flops)
+    return res
+
+
+def parallel_vectors(v, w, aux=None, spacing=1.0, vmin=0.0, wmin=0.0):
+    """The parallel-vectors operator of Peikert and Roth: the locus where the fields v and w of K steps are parallel, as
+    line segments (fs_pv_count3d, fs_pv_emit3d).  With w = J v these are the vortex core lines of Sujudi and Haimes,
+    with w = curl v those of Levy et al. (cores.core_fields forms both).  3-D only: in 2-D the locus is a curve.
+
+    v, w: [K,3,D,H,W] fp32 on a GPU, channel 0 along W, every extent >= 2; the step stride may be anything (stack[::2]
+    is read in place).  aux: optional [K,D,H,W] fp32, a scalar interpolated to every point (Q, lambda2: what segments
+    are filtered by).  spacing: the node spacing, one value or one per axis in the tensor's axis order (D,H,W).  vmin,
+    wmin: a node with |v| <= vmin or |w| <= wmin is quiet, and a face whose three corners are quiet holds nothing.
+
+    Every cell is cut into its six Kuhn tetrahedra and both fields taken as linear on each triangular face: the points
+    of a face where v || w are the real eigenvalues of a 3 x 3 pencil with an eigenvector inside the triangle.  A
+    tetrahedron with exactly two such points holds one segment; one with any other number but 0 is counted as
+    ambiguous and emits nothing, as is a face whose pencil is singular (degenerate).  A face is solved once, by the node
+    that owns it, so the two tetrahedra that share it agree bit for bit: segments that meet carry equal `key`s, and
+    cores.link_segments joins them into lines by key alone.  include/flowsci_hip.h states the order of operations;
+    tests/pv_ref.py restates it and agrees bit for bit.
+
+    The number of segments depends on the data, so this SYNCHRONISES: exactly once, between the two passes.  `status`
+    is returned, not read: ops.parallel_vectors_check(result) reads it.
+
+    Returns a dict on the device: cell (int32 [N]: the cell's node index within its step), simplex (uint8 [N]: t), face
+    (uint8 [N,2]: the face of t each endpoint lies on), key (int64 [N,2]: 4 * global face id + root rank), pos (fp32
+    [N,2,3]: (x, y, z) in physical units), mu (fp64 [N,2]: w = mu * v at the point), vel (fp32 [N,2,3]: v at the point),
+    aux (fp32 [N,2], only when given), offsets (int64 [K+1]: step k owns the rows offsets[k] .. offsets[k+1], ordered by
+    cell, then t), counts (int64 [K,4]: segments, ambiguous tetrahedra, degenerate faces, cells with a value that is not
+    finite) and status (int32 [1]).  Bitwise reproducible.  Nothing is differentiated."""
+    vmin, wmin = _pv_min("vmin", vmin), _pv_min("wmin", wmin)
+    v, w, aux = _pv_operands(v, w, aux)
+    sp, P = _lattice(v.shape[2:])
+    K = int(v.shape[0])
+    _cp_spacing_scale(spacing, 1.0, 3, K)
+    ws, off = parallel_vectors_count(v, w, aux, vmin, wmin)
+    rows = P // sp[-1]
+    R = K * rows
+    steps = off[::rows].contiguous()  # [K+1]
+    host = steps.cpu().numpy()  # the one synchronisation
+    res = parallel_vectors_emit(v, w, aux, spacing, vmin, wmin, ws, off, int(host[-1]))
+    per_row = ws[4 * R:16 * R].view(torch.int32).view(3, K, rows).sum(2, dtype=torch.int64)  # namb, ndeg, nnf
+    res["offsets"] = steps
+    res["counts"] = torch.cat([(steps[1:] - steps[:-1])[None], per_row], 0).t().contiguous()
+    return res
+
+
+def parallel_vectors_check(result):
+    """Raises FlowsciKernelError when ops.parallel_vectors' `status` is set (its two passes disagreed: the arrays are
+    then not a table).  Synchronises."""
+    st = int(result["status"].view(-1)[0]) if isinstance(result["status"], torch.Tensor) else int(result["status"])
+    if st != 0:
+        raise _lib.FlowsciKernelError("fs_pv_emit3d: the two passes disagree (status %d)" % st)
+
+
+# --------------------------------------------------------------------------------------------
 # Line integral convolution: a texture averaged along the streamlines of step flows (fs_lic{2,3}d)
 # --------------------------------------------------------------------------------------------
 LIC_FULL, LIC_OUT, LIC_STAGNANT, LIC_NONFINITE = 0, 1, 2, 3  # FS_LIC_*: how a side of a line ended
