@@ -67,7 +67,10 @@ enum {
  *   480  fs_streamlines2d / fs_streamlines3d (streamlines of step flows as geometry: every vertex kept, lines ended by
  *        the border, stagnation, a capturing cell or their length -- what separatrices are traced with).
  *   490  fs_pv_count3d / fs_pv_emit3d / fs_pv3d_ws_bytes (parallel vectors: the segments of the locus v || w on the Kuhn
- *        split -- vortex core lines after Sujudi-Haimes (w = J v) and Levy et al. (w = vorticity)). */
+ *        split -- vortex core lines after Sujudi-Haimes (w = J v) and Levy et al. (w = vorticity)).
+ *        Added without a new number (no existing argument list changed): fs_ridge_nodes3d / fs_ridge_count3d /
+ *        fs_ridge_emit3d / fs_ridge3d_ws_bytes (height-ridge surfaces of scalar volumes: Marching Ridges on the Kuhn
+ *        split).  A binding that needs them fails on a library without them when it resolves the symbols. */
 #define FS_ABI_VERSION 490
 int fs_version(void);
 /* Static string for an FS_* code. */
@@ -1414,6 +1417,99 @@ int fs_pv_emit3d(const float* v, long long v_sstride, const float* w, long long 
                  const unsigned char* ws, const long long* row_offsets, long long N, int* cell, unsigned char* simplex,
                  unsigned char* face, long long* key, float* pos, double* mu, float* vel, float* aux_out, int* status,
                  fs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Ridge surfaces -- K scalar volumes to K indexed triangle meshes of their height ridges of co-dimension one (Eberly:
+ * the points where the gradient is orthogonal to the eigenvector e of the Hessian's smallest eigenvalue lam, and lam is
+ * negative), extracted by Marching Ridges (Furst and Pagendarm) on the Kuhn split of every cell.  Of an FTLE field
+ * these are the Lagrangian coherent structures (Sadlo and Peikert 2007); with valley != 0 the valley surfaces.
+ *   volumes: K fp32 volumes of D*H*W nodes, node (z, y, x) at (z * H + y) * W + x, volume k at + k * sstride elements
+ *     (>= D*H*W); every extent >= 2.  Axis 0 runs along x (W), 1 along y, 2 along z.
+ *   inv_2h, inv_hh, inv_4hh: HOST arrays of 3 doubles: 1 / (2 h_c) and 1 / h_c^2 for c = x, y, z, and 1 / (4 h_a h_b) for
+ *     ab = xy, xz, yz, with h the node spacing.  The host forms them in fp64; the device divides nothing by them.
+ *   valley != 0 negates every f as it is read (exactly): the valleys of f are the ridges of -f, bit for bit.
+ *
+ *   Node pass (fs_ridge_nodes3d), in fp64 without fused multiply-adds; f is widened to fp64 before any arithmetic.  A
+ *   restatement with the same operations in the same order reproduces every stored bit.  A node's class is the first
+ *   that applies:
+ *     FS_RIDGE_BORDER     an index is 0 or extent - 1 along some axis: nothing is extrapolated, the ridge stops one node
+ *                         inside.
+ *     FS_RIDGE_NONFINITE  one of the 19 stencil values -- the centre, the 6 axis neighbours, the 12 planar diagonals -- is
+ *                         not finite; or one of the five stored operands is not finite as fp32 (overflow).
+ *     FS_RIDGE_WEAK       !(lam <= -strength), strength >= 0.
+ *     FS_RIDGE_LOW        !(f >= fmin); fmin = -inf switches the filter off.
+ *     FS_RIDGE_ELIGIBLE   everything else.
+ *     g_c  = (f(+c) - f(-c)) * inv_2h[c]
+ *     H_cc = ((f(+c) - 2 f) + f(-c)) * inv_hh[c]
+ *     H_ab = ((f(+a+b) - f(+a-b)) - (f(-a+b) - f(-a-b))) * inv_4hh[ab]
+ *     Eigen-solve: A = H, V = I, then FS_RIDGE_SWEEPS cyclic Jacobi sweeps, each the rotations (p, q) = (0,1), (0,2),
+ *       (1,2) in this order, made of IEEE fp64 + - * / sqrt alone.  A rotation with a_pq == 0 changes nothing.  Else
+ *         theta = (a_qq - a_pp) / (2 a_pq);   t = 1 / (|theta| + sqrt(theta theta + 1)), negated when theta < 0
+ *         c = 1 / sqrt(t t + 1);   s = t c
+ *         a_pp' = a_pp - t a_pq;   a_qq' = a_qq + t a_pq;   a_pq' = 0
+ *         with r the third index   a_rp' = c a_rp - s a_rq;   a_rq' = s a_rp + c a_rq
+ *         for every row k of V     v_kp' = c v_kp - s v_kq;   v_kq' = s v_kp + c v_kq
+ *       Equal diagonals give theta = 0 and t = 1 (45 degrees); where theta theta overflows t is 0, c is 1 and the
+ *       rotation only clears a_pq, which is then below 2^-511 of the diagonals' difference.  Four sweeps are the fewest
+ *       after which |a01| + |a02| + |a12| is at most 2^-45 of H's Frobenius norm on every field of tests/ridge_fields.py
+ *       (three leave 6e-6, four 8e-23).
+ *     lam = the smallest diagonal entry of A (ties: the lowest index), e = that column of V with the sign it comes out
+ *       with, d = (e0 g0 + e1 g1) + e2 g2.
+ *   operands: fp32 [K][5][D*H*W] = e0, e1, e2, d, lam, each rounded once; NaN at nodes that are not ELIGIBLE.
+ *   cls: uint8 [K][D*H*W].
+ *
+ *   Marching pass (fs_ridge_count3d, fs_ridge_emit3d).  It reads the stored fp32 operands and classes only, so every
+ *   decision can be restated exactly.  Edges e0 .. e6 of the owner node and the six tetrahedra of a cell are those of
+ *   the isosurface block above.  For an edge (a, b), a the owner:
+ *     o = (ea0 eb0 + ea1 eb1) + ea2 eb2 in fp64;   flip = o < 0;   db' = flip ? -db : db
+ *     ACTIVE iff both ends are ELIGIBLE and signbit(da) != signbit(db') (sign bits, not comparisons: +-0 stay consistent
+ *     under negation).  An active edge carries one vertex:
+ *     t = da / (da - db') in fp64, 0.5 where the denominator is 0, clamped to [0, 1], rounded to fp32 once; the position
+ *     follows the isosurface block's formula and order in fp32 (spacing: HOST array of 3 doubles along x, y, z, each
+ *     rounded to fp32 once).  The orientation of e is decided per edge from its two ends alone, so every cell sharing an
+ *     edge sees the same vertex.
+ *   A tetrahedron (corners c0 .. c3) with a corner that is not ELIGIBLE emits nothing.  Otherwise sigma_0 = 0,
+ *     sigma_i = (e_c0 . e_ci < 0) for i = 1..3 (the same fp64 dot product), and the tetrahedron is TWISTED when for some
+ *     1 <= i < j <= 3 (e_ci . e_cj < 0) != (sigma_i xor sigma_j): e cannot be oriented consistently over it.  A twisted
+ *     tetrahedron emits nothing and is counted: a hole in the surface, reported, not an error.  Otherwise corner i is
+ *     inside iff !(signbit(d_ci) xor sigma_i), and the triangles are those of the isosurface block for that case
+ *     (csrc/iso_tables.hpp).  Every edge the case uses is then active.  The winding is the table's and means nothing
+ *     here: a ridge surface need not be orientable, and the sign of e is the solver's -- negating e and d at a node
+ *     turns the cases of its tetrahedra into their complements, which hold the same triangles on the same vertices
+ *     with the other winding (and, for two triangles, in the other order).
+ *   Vertices of a step are ordered by owner node index, then edge number; faces by cell index, tetrahedron, triangle,
+ *   as int32 vertex indices local to their step.  values_out (optional): fp32 [V][2] = f (negated under valley) and
+ *   the stored lam, each wa + t (wb - wa) in fp32; fused multiply-adds are allowed there.  The result is bitwise
+ *   reproducible: no atomic decides a position or an order.
+ *
+ * fs_ridge_nodes3d -- one launch.
+ * fs_ridge_count3d -- one launch.  ws: fs_ridge3d_ws_bytes bytes, 4-byte aligned, written as
+ *     int32 nv[K*D*H], nt[K*D*H], ntwisted[K*D*H], ntets[K*D*H]: per row (k, z, y) the vertices its nodes own, the
+ *     triangles its cells emit, their twisted tetrahedra and their tetrahedra with four ELIGIBLE corners;
+ *     uint8 mask[K][D*H*W]: bit e of a node's byte = its edge e is active.
+ * The caller turns nv and nt into row_offsets, int64 [2][K*D*H + 1] in DEVICE memory, as for fs_iso_emit3d.
+ * fs_ridge_emit3d -- one launch (none when V and T are 0) on the same operands; vertices [V][3], values_out [V][2] (NULL:
+ *   not wanted), faces int32 [T][3].  Nothing is written at or beyond row V or T.  status: int32 [1], zeroed by the
+ *   CALLER; bit 0 is set when the passes disagree (a mask that these operands do not give, a row's counts, an index
+ *   outside its step, a triangle on an edge that is not active) -- the outputs are then not a mesh.
+ *   FS_ERR_NULLPTR: volumes, the host arrays, operands, cls, ws, row_offsets or status NULL; vertices with V > 0, faces
+ *   with T > 0.  FS_ERR_SHAPE: K < 1 or K*D*H above 2^31 - 1, an extent below 2, more than 2^31 - 1 nodes, sstride below
+ *   D*H*W.  FS_ERR_ARG: an inv_2h, inv_hh, inv_4hh or spacing entry that is not finite and positive (spacing: as fp32),
+ *   strength negative or not finite, fmin NaN or +inf, V or T negative, ws not 4-byte aligned.  All of them are returned
+ *   before anything is launched; the _ws_bytes query launches nothing and returns the byte count or -(FS_ERR_*).
+ */
+#define FS_RIDGE_SWEEPS 4
+enum { FS_RIDGE_BORDER = 0, FS_RIDGE_NONFINITE = 1, FS_RIDGE_WEAK = 2, FS_RIDGE_LOW = 3, FS_RIDGE_ELIGIBLE = 4 };
+long long fs_ridge3d_ws_bytes(int K, int D, int H, int W);
+int fs_ridge_nodes3d(const float* volumes, int K, int D, int H, int W, long long sstride, int valley,
+                     const double* inv_2h, const double* inv_hh, const double* inv_4hh, double strength, double fmin,
+                     float* operands, unsigned char* cls, fs_stream_t stream);
+int fs_ridge_count3d(const float* operands, const unsigned char* cls, int K, int D, int H, int W, unsigned char* ws,
+                     fs_stream_t stream);
+int fs_ridge_emit3d(const float* volumes, int K, int D, int H, int W, long long sstride, int valley,
+                    const float* operands, const unsigned char* cls, const double* spacing, const unsigned char* ws,
+                    const long long* row_offsets, long long V, long long T, float* vertices, float* values_out,
+                    int* faces, int* status, fs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Training batches out of a stored time series -- Flow-3D/load_datasets.py:29-190 `load_data` (un-pickle, nan_to_num,

@@ -196,6 +196,11 @@ SIGNATURES = {
     "fs_pv_count3d": [_f32p, _i64, _f32p, _i64, _f32p, _i64] + [_int] * 4 + [_double, _double, _f32p, _stream],
     "fs_pv_emit3d": [_f32p, _i64, _f32p, _i64, _f32p, _i64] + [_int] * 4 + [_f64p, _double, _double, _f32p, _f32p, _i64] +
                     [_f32p] * 9 + [_stream],
+    "fs_ridge3d_ws_bytes": [_int] * 4,
+    "fs_ridge_nodes3d": [_f32p] + [_int] * 4 + [_i64, _int, _f64p, _f64p, _f64p, _double, _double, _f32p, _f32p, _stream],
+    "fs_ridge_count3d": [_f32p, _f32p] + [_int] * 4 + [_f32p, _stream],
+    "fs_ridge_emit3d": [_f32p] + [_int] * 4 + [_i64, _int, _f32p, _f32p, _f64p, _f32p, _f32p, _i64, _i64] + [_f32p] * 4 +
+                       [_stream],
     "fs_triplet_gather": [_f32p, _int, _i64, _int, _int, _int, _f32p, _int, _int, _int, _int, _f32p, _stream],
     "fs_series_stats_ws_bytes": [_int, _i64],
     "fs_series_stats": [_f32p, _int, _int, _i64, _f32p, _f32p, _stream],
@@ -217,7 +222,7 @@ _RESTYPES = {"fs_error_string": ctypes.c_char_p, "fs_conv3d_fwd_ws_floats": ctyp
              "fs_raycast3d_ws_bytes": ctypes.c_longlong, "fs_iso3d_ws_bytes": ctypes.c_longlong,
              "fs_lic2d_ws_bytes": ctypes.c_longlong, "fs_lic3d_ws_bytes": ctypes.c_longlong,
              "fs_critical2d_ws_bytes": ctypes.c_longlong, "fs_critical3d_ws_bytes": ctypes.c_longlong,
-             "fs_pv3d_ws_bytes": ctypes.c_longlong,
+             "fs_pv3d_ws_bytes": ctypes.c_longlong, "fs_ridge3d_ws_bytes": ctypes.c_longlong,
              "fs_series_stats_ws_bytes": ctypes.c_longlong, "fs_series_encode_ws_bytes": ctypes.c_longlong,
              "fs_conv3d_tr_ws_floats": ctypes.c_longlong, "fs_conv3d_fwd_dprelu_part_floats": ctypes.c_longlong,
              "fs_conv3d_fwd_dprelu_part_floats_k3": ctypes.c_longlong}
@@ -249,7 +254,10 @@ def lib():
         try:
             fn = getattr(handle, name)
         except AttributeError as e:
-            raise FlowsciLibraryError("libflowsci_hip.so does not export %s" % name) from e
+            raise FlowsciLibraryError(
+                "libflowsci_hip.so at %s does not export %s: it was built from an older include/flowsci_hip.h "
+                "(symbols are added without a new FS_ABI_VERSION) -- rebuild with "
+                "`make -C opticalflowscivis_amd/csrc`" % (LIB_PATH, name)) from e
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, _int)
     got = handle.fs_version()

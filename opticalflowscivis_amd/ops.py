@@ -4059,6 +4059,194 @@ def parallel_vectors_check(result):
 
 
 # --------------------------------------------------------------------------------------------
+# Ridge surfaces: the height ridges (of an FTLE field: the LCS) and valleys of scalar volumes as triangle meshes
+# (fs_ridge_nodes3d, fs_ridge_count3d, fs_ridge_emit3d)
+# --------------------------------------------------------------------------------------------
+RIDGE_BORDER, RIDGE_NONFINITE, RIDGE_WEAK, RIDGE_LOW, RIDGE_ELIGIBLE = 0, 1, 2, 3, 4  # FS_RIDGE_*: a node's class
+RIDGE_CLASS_NAMES = ("border", "nonfinite", "weak", "low", "eligible")
+RIDGE_SWEEPS = 4  # FS_RIDGE_SWEEPS
+
+
+def ridge_cost(shape, K=1, V=0, T=0, op="nodes", values=True):
+    """(HBM bytes, flops) the algorithm needs for one pass of ops.ridge_surfaces over K volumes of spatial `shape`.
+    "nodes": every node read once (4 bytes; its 18 neighbours come out of the caches), five fp32 operands and a class
+    byte written; ~600 fp64 flops per interior node (19-point differences, 4 sweeps of 3 rotations of ~45 flops, 15 of
+    them divisions and square roots counted as one).  "count": four operands and the class of every node read (17
+    bytes), its mask byte written, four int32 per row; 19 fp64 dot products per eligible cell.  "emit": the mask bytes
+    read, the V vertices (12 bytes, 8 more with values) and T faces (12 bytes) written; the operands gathered around
+    cut cells are on top and depend on the surface."""
+    sp = tuple(int(s) for s in shape)
+    if len(sp) != 3 or min(sp) < 2:
+        raise ValueError("shape must be (D,H,W) with every extent >= 2, got %r" % (shape,))
+    K, V, T = int(K), int(V), int(T)
+    if K < 1 or V < 0 or T < 0:
+        raise ValueError("K >= 1 and V, T >= 0, got %d, %d, %d" % (K, V, T))
+    P = sp[0] * sp[1] * sp[2]
+    if op == "nodes":
+        return K * 25 * P, K * 600 * max(sp[0] - 2, 0) * max(sp[1] - 2, 0) * max(sp[2] - 2, 0)
+    if op == "count":
+        return K * (18 * P + 16 * sp[0] * sp[1]), K * 95 * P
+    if op == "emit":
+        return K * P + V * (12 + (8 if values else 0)) + 12 * T, 0
+    raise ValueError("op must be 'nodes', 'count' or 'emit', got %r" % (op,))
+
+
+def _ridge_filters(strength, fmin):
+    try:
+        strength, fmin = float(strength), float(fmin)
+    except (TypeError, ValueError):
+        raise ValueError("strength and fmin must be numbers, got %r and %r" % (strength, fmin))
+    if not 0 <= strength < float("inf"):
+        raise ValueError("strength must be finite and >= 0, got %r" % (strength,))
+    if not fmin < float("inf"):
+        raise ValueError("fmin must be a number below +inf (-inf: no filter), got %r" % (fmin,))
+    return strength, fmin
+
+
+def _ridge_operands(operands, cls):
+    if not (isinstance(operands, torch.Tensor) and isinstance(cls, torch.Tensor) and operands.is_cuda and
+            operands.dtype == torch.float32 and cls.dtype == torch.uint8 and operands.dim() == 5 and cls.dim() == 4 and
+            operands.shape[1] == 5 and tuple(operands.shape[2:]) == tuple(cls.shape[1:]) and
+            operands.shape[0] == cls.shape[0] and cls.device == operands.device):
+        raise ValueError("operands must be float32 [K,5,D,H,W] and cls uint8 [K,D,H,W] on one GPU, as ops.ridge_nodes "
+                         "returns them")
+    K = int(cls.shape[0])
+    sp = tuple(int(s) for s in cls.shape[1:])
+    if K < 1 or min(sp) < 2:
+        raise ValueError("every extent must be >= 2, got %s" % (tuple(cls.shape),))
+    return operands.detach().contiguous(), cls.detach().contiguous(), K, sp, sp[0] * sp[1] * sp[2]
+
+
+def ridge_nodes(volumes, spacing=1.0, strength=0.0, fmin=-float("inf"), valley=False):
+    """The node pass of ops.ridge_surfaces on its own (fs_ridge_nodes3d, one launch): per node of fp32 volumes [K,D,H,W]
+    the gradient and Hessian by central differences and the Hessian's smallest eigenvalue lam with its eigenvector e, in
+    fp64.  Returns (operands fp32 [K,5,D,H,W] = e_x, e_y, e_z, d = e . grad f, lam -- NaN where the node is not eligible
+    -- and cls uint8 [K,D,H,W], RIDGE_*: border, a stencil value that is not finite, weak (!(lam <= -strength)), low
+    (!(f >= fmin)), eligible).  valley: the same of -f.  Never synchronises."""
+    volumes, K, sp, P = _rc_volumes(volumes)
+    hs = _rc_spacing(spacing)[::-1]  # along x, y, z
+    strength, fmin = _ridge_filters(strength, fmin)
+    dev = volumes.device
+    operands = torch.empty((K, 5) + sp, dtype=torch.float32, device=dev)
+    cls = torch.empty((K,) + sp, dtype=torch.uint8, device=dev)
+    inv_2h = (ctypes.c_double * 3)(*[1.0 / (2.0 * h) for h in hs])
+    inv_hh = (ctypes.c_double * 3)(*[1.0 / (h * h) for h in hs])
+    inv_4hh = (ctypes.c_double * 3)(1.0 / (4.0 * hs[0] * hs[1]), 1.0 / (4.0 * hs[0] * hs[2]), 1.0 / (4.0 * hs[1] * hs[2]))
+    nbytes, flops = ridge_cost(sp, K, op="nodes")
+    with torch.cuda.device(dev):
+        _call("fs_ridge_nodes3d", volumes.data_ptr(), K, *sp, volumes.stride(0) if K > 1 else P, 1 if valley else 0,
+              inv_2h, inv_hh, inv_4hh, strength, fmin, operands.data_ptr(), cls.data_ptr(), _stream(volumes),
+              algo_bytes=nbytes, algo_flops=flops)
+    return operands, cls
+
+
+def ridge_count(operands, cls):
+    """The first marching pass on its own (fs_ridge_count3d) on what ops.ridge_nodes returned: the workspace (uint8: per
+    row its vertices, triangles, twisted and all-eligible tetrahedra as int32, then the per-node masks of active edges)
+    and row_offsets, int64 [2, K*D*H + 1] on the device (plumbing: torch.cumsum).  Never synchronises."""
+    operands, cls, K, sp, P = _ridge_operands(operands, cls)
+    dev = operands.device
+    R = K * sp[0] * sp[1]
+    nb = _lib.lib().fs_ridge3d_ws_bytes(K, *sp)
+    if nb < 0:
+        _lib.check(int(-nb), "fs_ridge3d_ws_bytes")
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    nbytes, flops = ridge_cost(sp, K, op="count")
+    with torch.cuda.device(dev):
+        _call("fs_ridge_count3d", operands.data_ptr(), cls.data_ptr(), K, *sp, ws.data_ptr(), _stream(operands),
+              algo_bytes=nbytes, algo_flops=flops)
+    off = torch.zeros((2, R + 1), dtype=torch.int64, device=dev)
+    off[:, 1:] = torch.cumsum(ws[:8 * R].view(torch.int32).view(2, R), 1, dtype=torch.int64)
+    return ws, off
+
+
+def ridge_emit(volumes, operands, cls, spacing, valley, ws, row_offsets, V, T, values=True):
+    """The second marching pass on its own (fs_ridge_emit3d), on what ridge_nodes and ridge_count returned and the
+    totals V and T as host ints.  Returns (vertices, values or None, faces, status) on the device.  Never synchronises;
+    launches nothing when V and T are 0."""
+    volumes, K, sp, P = _rc_volumes(volumes)
+    operands, cls, K2, sp2, _ = _ridge_operands(operands, cls)
+    if (K2, sp2) != (K, sp) or operands.device != volumes.device:
+        raise ValueError("operands and cls must be those of these volumes (%d x %s), got %d x %s" % (K, sp, K2, sp2))
+    hs = _rc_spacing(spacing)
+    dev = volumes.device
+    V, T = int(V), int(T)
+    vert = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    vout = torch.empty((V, 2), dtype=torch.float32, device=dev) if values else None
+    faces = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if V or T:
+        nbytes, flops = ridge_cost(sp, K, V, T, op="emit", values=values)
+        with torch.cuda.device(dev):
+            _call("fs_ridge_emit3d", volumes.data_ptr(), K, *sp, volumes.stride(0) if K > 1 else P, 1 if valley else 0,
+                  operands.data_ptr(), cls.data_ptr(), (ctypes.c_double * 3)(*hs[::-1]), ws.data_ptr(),
+                  row_offsets.data_ptr(), V, T, vert.data_ptr(), _ptr(vout), faces.data_ptr(), status.data_ptr(),
+                  _stream(volumes), algo_bytes=nbytes, algo_flops=flops)
+    return vert, vout, faces, status
+
+
+def ridge_surfaces(volumes, spacing=1.0, strength=0.0, fmin=-float("inf"), valley=False, values=True):
+    """The height-ridge surfaces of K scalar volumes as K indexed triangle meshes, three launches (fs_ridge_nodes3d,
+    fs_ridge_count3d, fs_ridge_emit3d): the points where the gradient is orthogonal to the eigenvector e of the Hessian's
+    smallest eigenvalue lam and lam <= -strength (Eberly), extracted by Marching Ridges on the Kuhn split of every cell.
+    Of an FTLE field (ops.ftle) these are the Lagrangian coherent structures -- repelling ones of a forward field,
+    attracting ones of a backward field; valley=True gives the valley surfaces (of lambda2, of a density).  3-D only: in
+    2-D ridges are curves.
+
+    volumes: fp32 [K,D,H,W] on a GPU, every extent >= 2; the step stride may be anything.  spacing: the node spacing, one
+    value or (D,H,W).  strength >= 0: the least -lam of a ridge node, in units of f / spacing^2.  fmin: nodes with
+    f < fmin carry no ridge (-inf: no filter); under valley it applies to -f.  Border nodes carry none either: the
+    surface stops one node inside, and next to nodes that are not finite.
+
+    The sign of an eigenvector is arbitrary, so d = e . grad f has no sign of its own: it is oriented per edge from the
+    edge's two ends, which makes every cell around an edge agree on its vertex.  A tetrahedron over which e cannot be
+    oriented consistently (near degenerate eigenvalues; most of white noise) is TWISTED: it emits nothing and is
+    counted -- a hole, not an error.  include/flowsci_hip.h states the definition; tests/ridge_ref.py restates it and
+    agrees bit for bit.
+
+    The numbers of vertices and faces depend on the data, so this SYNCHRONISES: exactly once, between the last two
+    launches.  `status` is returned, not read: ops.ridge_surfaces_check(result) reads it.  ValueError when a step has
+    2^31 - 1 or more vertices or faces.
+
+    Returns a dict on the device: vertices (fp32 [V,3], (x, y, z)), values (fp32 [V,2]: f -- negated under valley -- and
+    lam at the vertex; only with values), faces (int32 [T,3], indices local to their step; the winding means nothing: a
+    ridge surface need not be orientable), vertex_offsets and face_offsets (int64 [K+1]), counts (int64 [K,4]: vertices,
+    faces, twisted tetrahedra, tetrahedra with four eligible corners), classes (int64 [K,5]: nodes per RIDGE_* class),
+    operands and cls (what ops.ridge_nodes returned) and status (int32 [1]).  Bitwise reproducible.  Nothing is
+    differentiated."""
+    volumes, K, sp, P = _rc_volumes(volumes)
+    _rc_spacing(spacing)
+    operands, cls = ridge_nodes(volumes, spacing, strength, fmin, valley)
+    ws, off = ridge_count(operands, cls)
+    rows = sp[0] * sp[1]
+    R = K * rows
+    steps = off[:, ::rows].contiguous()  # [2, K+1]
+    host = steps.cpu().numpy()  # the one synchronisation
+    per_step = _np.diff(host, axis=1)
+    if per_step.size and int(per_step.max()) >= 2 ** 31 - 1:
+        raise ValueError("a step has %d vertices or faces: the limit is 2^31 - 2" % int(per_step.max()))
+    V, T = int(host[0, -1]), int(host[1, -1])
+    vert, vout, faces, status = ridge_emit(volumes, operands, cls, spacing, valley, ws, off, V, T, values)
+    per_row = ws[:16 * R].view(torch.int32).view(4, K, rows).sum(2, dtype=torch.int64)
+    flat = cls.view(K, -1)
+    res = {"vertices": vert, "faces": faces, "vertex_offsets": steps[0], "face_offsets": steps[1],
+           "counts": per_row.t().contiguous(),
+           "classes": torch.stack([(flat == c).sum(1) for c in range(5)], 1), "operands": operands, "cls": cls,
+           "status": status}
+    if values:
+        res["values"] = vout
+    return res
+
+
+def ridge_surfaces_check(result):
+    """Raises FlowsciKernelError when ops.ridge_surfaces' `status` is set (its marching passes disagreed: the arrays are
+    then not a mesh).  Synchronises."""
+    st = int(result["status"].view(-1)[0]) if isinstance(result["status"], torch.Tensor) else int(result["status"])
+    if st != 0:
+        raise _lib.FlowsciKernelError("fs_ridge_emit3d: the marching passes disagree (status %d)" % st)
+
+
+# --------------------------------------------------------------------------------------------
 # Line integral convolution: a texture averaged along the streamlines of step flows (fs_lic{2,3}d)
 # --------------------------------------------------------------------------------------------
 LIC_FULL, LIC_OUT, LIC_STAGNANT, LIC_NONFINITE = 0, 1, 2, 3  # FS_LIC_*: how a side of a line ended
